@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — micro-image observations/second through one Jacobian+Schur sweep (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--full] [--dump-outputs DIR]
 
 A "step" is one lifcal_ba sweep (tables + residual/Jacobian/robust-weight accumulation + point-block
 elimination + reduced system) over observations already resident in HBM.
@@ -15,11 +15,15 @@ point by the library); `--scaling strong --workload cfg4` shards ONE problem (BA
 exchange is the reduced normal equations per sweep, on the library's own RCCL communicator; if that cannot be set up the run
 FAILS unless --allow-comm-fallback is given (a scaling number is never silently the fallback's).
 Timing: `--preheat-ms` (default 150) of untimed sweeps bring the GPU to its sustained clocks (the same kernel is 5 % slower in the
-first milliseconds after idle), then W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize pairs; every 8th
-timed step carries the dominant kernel's own start / stop events (a stamped launch costs ~5 us of queue time).
-Rank 0 prints ONE JSON line.  `value` is whole-job obs/s; `roofline` prices the dominant kernel
-against the 8 TB/s HBM peak with the algorithmic bytes of DESIGN.md; `cpu_baseline` times the CPU
-restatement (oracle/, kind "port") on a bounded sample of the same workload on this host's cores.
+first milliseconds after idle), then W untimed warm-up steps, then EXACTLY K steps between barrier + synchronize pairs.
+Rank 0 prints ONE JSON line.  `value` is whole-job obs/s, `ms_per_step` the wall time of one timed step.
+A plain run does only that.  `--full` adds everything else, as one run: every 8th timed step carries the dominant kernel's own
+start / stop events (a stamped launch costs ~5 us of queue time) for `roofline`, which prices the dominant kernel against the
+8 TB/s HBM peak with the algorithmic bytes of DESIGN.md; `solve` is the full LM solve after the timed steps; `cpu_baseline` times the
+CPU restatement (oracle/, kind "port") on the same workload on this host's cores and `parity` checks the GPU sweep against it
+(`--no-solve` / `--no-cpu-baseline` leave those out of a --full run).
+`--dump-outputs DIR` writes what the timed sweep hands its caller (lifcal_ba_sweep: cost, reduced system, gradients) as
+DIR/<name>.npy in float64 after the timed steps; the inputs are generated from fixed seeds, so two builds compare output for output.
 """
 from __future__ import annotations
 
@@ -136,6 +140,26 @@ def load_traffic(workload):
         return None, None
 
 
+DUMP_BYTES = 64_000_000   # --dump-outputs: all arrays together
+
+
+def dump_outputs(dirname, arrays):
+    """Writes each array as dirname/<name>.npy in float64.  If they do not fit DUMP_BYTES together (the dense reduced system of a
+    weak-scaled N > 1 run), the small ones stay whole and the large ones share the rest: each is cut to the same seeded, sorted
+    sample of flat positions in every run with the same arguments."""
+    os.makedirs(dirname, exist_ok=True)
+    arrays = {k: np.ascontiguousarray(v, dtype=np.float64).reshape(-1) for k, v in arrays.items()}
+    room = DUMP_BYTES - 256 * len(arrays)   # (.npy headers)
+    keep = {}
+    for i, (name, a) in enumerate(sorted(arrays.items(), key=lambda kv: kv[1].size)):
+        keep[name] = min(a.size, room // 8 // (len(arrays) - i))
+        room -= 8 * keep[name]
+    for name, a in arrays.items():
+        if keep[name] < a.size:
+            a = a[np.sort(np.random.default_rng(0).choice(a.size, keep[name], replace=False))]
+        np.save(os.path.join(dirname, name + ".npy"), a)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -155,8 +179,14 @@ def main():
                     help="0: fp64 everywhere (the BASELINE metric configuration); 1: options.precision = 1, residual / Jacobian of an observation in fp32 "
                          "(fp32 observation words + fp32 lens table), all accumulation and the solve in fp64 (BASELINE configs[4]'s arithmetic)")
     ap.add_argument("--deterministic", action="store_true", help="options.deterministic = 1: ordered reductions, bitwise reproducible (slower)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-solve", action="store_true", help="skip the full LM solve after the timed sweeps (profiling runs: only sweep kernels in the trace)")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline figure: the dominant kernel's time stamps and the roofline, the full LM solve, the CPU baseline "
+                         "and the in-run parity check against it (off by default: a plain run only sets up, warms up and times the K steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="after the timed steps write what the timed sweep returns to its caller (cost, S, rhs, gradients; lifcal_ba_sweep) "
+                         "as DIR/<name>.npy, float64, at most 64 MB in all (a fixed seeded sample of a larger output)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check against it")
+    ap.add_argument("--no-solve", action="store_true", help="--full: skip the full LM solve after the timed sweeps (profiling runs: only sweep kernels in the trace)")
     ap.add_argument("--comm", choices=["rccl", "gloo"], default="rccl",
                     help="rccl: library-owned RCCL communicator (default, one GPU per rank); gloo: rehearsal of the multi-process path on ONE GPU (all ranks on cuda:0, all-reduce through host memory)")
     ap.add_argument("--allow-comm-fallback", action="store_true",
@@ -336,28 +366,38 @@ def main():
     for _ in range(args.warmup):
         ba.sweep_enqueue(radius)
     ba.sweep(radius)
-    # every 8th timed sweep carries the dominant kernel's own start / stop events (HIP events written by the dispatch packet, on the
-    # library's stream): a stamped launch costs ~5 us of queue time, so stamping all K of them would add 4 % to the very steps being timed
-    prof_stride = 8 if args.steps >= 16 else 1
-    ba.profile_begin(args.steps, prof_stride)
+    prof = None
+    if args.full:
+        # every 8th timed sweep carries the dominant kernel's own start / stop events (HIP events written by the dispatch packet, on the
+        # library's stream): a stamped launch costs ~5 us of queue time, so stamping all K of them would add 4 % to the very steps being timed
+        prof_stride = 8 if args.steps >= 16 else 1
+        ba.profile_begin(args.steps, prof_stride)
     barrier()
     t0 = time.perf_counter()
     for _ in range(args.steps):
         ba.sweep_enqueue(radius)
-    prof = ba.profile_end()                        # synchronises the library's stream
-    barrier()
+    if args.full:
+        prof = ba.profile_end()                    # synchronises the library's stream
+    barrier()                                      # (the device synchronise waits for the library's stream too: one HIP runtime in the process)
     dt = time.perf_counter() - t0
     if dist is not None:
         t = torch.tensor([dt], dtype=torch.float64, device="cpu" if args.comm == "gloo" else "cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
-    last = ba.sweep(radius, want_matrices=(world == 1 and not args.no_cpu_baseline))   # (matrices: the in-run cross-check against the CPU restatement below)
-    assert abs(last.cost - first.cost) <= 1e-9 * abs(first.cost), "sweep is not idempotent"
+    # the sweep on the unchanged point and radius returns what every timed step computed (matrices: the dumped outputs, and the
+    # in-run cross-check of --full against the CPU restatement below)
+    last = ba.sweep(radius, want_matrices=bool(args.dump_outputs and rank == 0) or (args.full and world == 1 and not args.no_cpu_baseline))
+    if args.full:
+        assert abs(last.cost - first.cost) <= 1e-9 * abs(first.cost), "sweep is not idempotent"
+    if args.dump_outputs and rank == 0:
+        outputs = {"cost": [last.cost], "gradient_max_norm": [last.gradient_max_norm]}
+        outputs.update((k, getattr(last, k)) for k in ("S", "rhs", "gradient_reduced", "point_gradient", "point_hessian_inv"))
+        dump_outputs(args.dump_outputs, outputs)
 
     # second half of the BASELINE metric: final RMS reprojection error after the full LM solve (outside the timed region)
     # (N = 1 only, like the CPU baseline: the weak-scaled N > 1 problem is a different scene; never let it cost the bench line)
     solve = None
-    if world == 1 and not args.no_solve:
+    if args.full and world == 1 and not args.no_solve:
         try:
             before = ba.calcReprojectionError(1.0)
             torch.cuda.synchronize()
@@ -381,18 +421,6 @@ def main():
         F_tot, P_tot = spec.n_frames * copies, spec.n_points * copies
         n_loc = info.n_obs_local
         n_red = 17 + 6 * F_tot
-        p_loc = info.n_points_local if strong else spec.n_points   # per-rank share of the algorithmic bytes (rank 0's shard)
-        b_obs = 24 if args.precision == 1 else 40   # SURVEY.md 8(d); the fp32 stream this library reads is 12 B per observation (du, dv, lens index)
-        b_kernel = accumulate_kernel_bytes(n_loc, p_loc, spec.n_frames, b_obs)
-        n_red_loc = 17 + 6 * spec.n_frames
-        # what the band + arrow layout of the reduced system stores: F (bw + 1) pose blocks of 36 + (NA + 1) arrow rows
-        nc_live = 5 + (spec.config & 3) + (2 if spec.config & 4 else 0)
-        na = nc_live + 3 * int(info.n_promoted)
-        stored_doubles = F_tot * int(info.max_window_frames) * 36 + (na + 1) * (6 * F_tot + na + 1)
-        b_sweep = algorithmic_bytes(n_loc, p_loc, spec.n_frames, n_red_loc, b_obs)
-        t_kernel = prof.ms_accumulate * 1e-3
-        t_total = prof.ms_total * 1e-3
-        achieved = b_kernel / t_kernel / 1e9
         out = {
             "metric": "micro-image obs/sec through Jacobian+Schur at 1M obs",
             "value": n_obs_total * args.steps / dt,
@@ -405,28 +433,42 @@ def main():
                        "workload": f"{args.workload}: {F_tot} frames, {P_tot} points, {n_obs_total} micro-image observations, "
                                    f"window {spec.window}, config {spec.config:#x} (2 radial + tangential, mlCenterAdj, Cauchy(0.5), refine poses+points)",
                        "obs_per_gpu": n_loc, "n_reduced": n_red, "sharding": "by 3D point" if world > 1 else "single GPU", "comm": comm_used,
-                       "exchange_ms_per_sweep": (prof.ms_exchange if world > 1 else None), "preheat_ms": args.preheat_ms,
+                       "exchange_ms_per_sweep": (prof.ms_exchange if world > 1 and prof is not None else None), "preheat_ms": args.preheat_ms,
                        "deterministic": bool(args.deterministic)},
-            "roofline": {"bound": "hbm", "kernel": "k_sweep (residual+Jacobian+block accumulation)",
-                         "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved * 1e9 / HBM_PEAK,
-                         "traffic": load_traffic(args.workload)[0], "traffic_source": load_traffic(args.workload)[1],
-                         "algorithmic_bytes_per_launch": b_kernel, "kernel_ms": prof.ms_accumulate,
-                         "kernel_launches_timed": int(prof.n_sampled),   # of the K timed steps (every 8th: see profile_begin above)
-                         "special_points": int(prof.special_points),   # points on the global-atomic kernels (their time is in ms_outside_dominant_kernel)
-                         "whole_sweep": {"algorithmic_bytes": b_sweep, "ms": prof.ms_total, "ms_outside_dominant_kernel": prof.ms_schur,
-                                         "achieved": b_sweep / t_total / 1e9, "frac": b_sweep / t_total / HBM_PEAK,
-                                         # SURVEY's formula charges S dense (n_red (n_red + 1) / 2 doubles); the band + arrow layout stores this much of it:
-                                         "bytes_moved_actual": b_sweep - 8 * (n_red_loc * (n_red_loc + 1) // 2) + 8 * stored_doubles}},
             "cost": last.cost,
-            "solve": solve,
         }
-        out["roofline"]["fp64_valu"] = {"flop_per_obs": FP64_FLOP_PER_OBS, "achieved": FP64_FLOP_PER_OBS * n_loc / t_kernel / 1e12,
-                                        "peak": FP64_PEAK / 1e12, "unit": "TFLOP/s", "frac": FP64_FLOP_PER_OBS * n_loc / t_kernel / FP64_PEAK}
+        if args.full:
+            p_loc = info.n_points_local if strong else spec.n_points   # per-rank share of the algorithmic bytes (rank 0's shard)
+            b_obs = 24 if args.precision == 1 else 40   # SURVEY.md 8(d); the fp32 stream this library reads is 12 B per observation (du, dv, lens index)
+            b_kernel = accumulate_kernel_bytes(n_loc, p_loc, spec.n_frames, b_obs)
+            n_red_loc = 17 + 6 * spec.n_frames
+            # what the band + arrow layout of the reduced system stores: F (bw + 1) pose blocks of 36 + (NA + 1) arrow rows
+            nc_live = 5 + (spec.config & 3) + (2 if spec.config & 4 else 0)
+            na = nc_live + 3 * int(info.n_promoted)
+            stored_doubles = F_tot * int(info.max_window_frames) * 36 + (na + 1) * (6 * F_tot + na + 1)
+            b_sweep = algorithmic_bytes(n_loc, p_loc, spec.n_frames, n_red_loc, b_obs)
+            t_kernel = prof.ms_accumulate * 1e-3
+            t_total = prof.ms_total * 1e-3
+            achieved = b_kernel / t_kernel / 1e9
+            out["roofline"] = {"bound": "hbm", "kernel": "k_sweep (residual+Jacobian+block accumulation)",
+                               "achieved": achieved, "peak": HBM_PEAK / 1e9, "unit": "GB/s", "frac": achieved * 1e9 / HBM_PEAK,
+                               "traffic": load_traffic(args.workload)[0], "traffic_source": load_traffic(args.workload)[1],
+                               "algorithmic_bytes_per_launch": b_kernel, "kernel_ms": prof.ms_accumulate,
+                               "kernel_launches_timed": int(prof.n_sampled),   # of the K timed steps (every 8th: see profile_begin above)
+                               "special_points": int(prof.special_points),   # points on the global-atomic kernels (their time is in ms_outside_dominant_kernel)
+                               "whole_sweep": {"algorithmic_bytes": b_sweep, "ms": prof.ms_total, "ms_outside_dominant_kernel": prof.ms_schur,
+                                               "achieved": b_sweep / t_total / 1e9, "frac": b_sweep / t_total / HBM_PEAK,
+                                               # SURVEY's formula charges S dense (n_red (n_red + 1) / 2 doubles); the band + arrow layout stores this much of it:
+                                               "bytes_moved_actual": b_sweep - 8 * (n_red_loc * (n_red_loc + 1) // 2) + 8 * stored_doubles}}
+            out["roofline"]["fp64_valu"] = {"flop_per_obs": FP64_FLOP_PER_OBS, "achieved": FP64_FLOP_PER_OBS * n_loc / t_kernel / 1e12,
+                                            "peak": FP64_PEAK / 1e12, "unit": "TFLOP/s", "frac": FP64_FLOP_PER_OBS * n_loc / t_kernel / FP64_PEAK}
+            out["solve"] = solve
     ba.close()
     if rank == 0:
-        out["cpu_baseline"] = None
-        out["parity"] = None
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            out["cpu_baseline"] = None
+            out["parity"] = None
+        if args.full and not args.no_cpu_baseline and world == 1:
             try:
                 out["cpu_baseline"], ref = cpu_baseline(sc, capi.ProblemArrays.from_scene(sc))
                 # GPU sweep against the CPU restatement on the identical input, in this very run (tests/test_gpu_scale.py asserts the bars)

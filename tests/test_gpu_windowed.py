@@ -74,7 +74,8 @@ def oracle_windowed(sc, pa, window, overlap):
         if k > 0:
             mask[:min(b - a, overlap)] = 1
         oracle.set_fixed_frames(mask)
-        s = oracle.solve(sub, threads=4)
+        s = oracle.solve(sub, threads=1)   # one thread: the oracle's Schur elimination adds blocks under locks in arrival order, and with
+                                           # several threads that rounding changes from run to run (fuzz seed 15009: the views by 1.4e-6)
         oracle.set_fixed_frames(None)
         pa.cam[:] = sub.cam; pa.views[6 * a:6 * b] = sub.views; pa.pts.reshape(-1, 3)[ids] = sub.pts.reshape(-1, 3)
         reports.append((a, b - a, len(ids), len(sel), s.iterations, s.termination))
