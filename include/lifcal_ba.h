@@ -223,6 +223,43 @@ int lifcal_ba_reproj_stats(lifcal_ba_handle* h, double inlier_threshold, lifcal_
  * With world_size > 1 a rank fills the observations of the points it owns and leaves NaN elsewhere. */
 int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* y_proj);
 
+/* ---- covariance of the parameters ----
+ * Evaluated at the device-resident parameters (like lifcal_ba_reproj_stats) on the UNDAMPED Gauss-Newton matrix H of the reduced
+ * system: Ceres semantics (robust loss through the corrector, points eliminated as in the solve), G = H^- for unit-variance pixel
+ * residuals.  With poses and points both refined and no frame held constant, one gauge frame is held constant for the call: that
+ * removes the six rigid directions of the scene.  What is left of the null space (the arrow Schur complement C: camera slots +
+ * promoted points) is measured on the Jacobi-scaled C: eigenvalues below null_rcond * lambda_max count as null, and G uses the
+ * pseudo-inverse of the rest.  A camera slot is ESTIMABLE when the null directions have no component on it (relative size
+ * <= estimable_tol in the scaled coordinates); the variance of an estimable slot does not depend on the g-inverse chosen.
+ * Pose blocks are relative to the gauge frame (and to the minimum-norm choice in the scaled coordinates of C).  Fixed slots,
+ * structurally absent slots, constant poses and the gauge frame are zero rows / columns.  The handle is left as it was: fixed-frame
+ * mask, Jacobi scaling state, LM state and parameters.  One rank, options.precision = 0, the LDS-window band factorisation. */
+typedef struct lifcal_ba_covariance_options {
+  int32_t gauge_frame;                 /* -1: automatic (first observed frame, when a gauge exists), >= 0: this frame, -2: none      */
+  int32_t want_pose_blocks;            /* 1: fill out->pose                                                                          */
+  int32_t scale_by_residual_variance;  /* 1: multiply G by sigma2 = 2 cost / (m - r) (an approximation under the Cauchy loss)       */
+  int32_t reserved;
+  double null_rcond;                   /* 1e-9: eigenvalue threshold of the scaled C, relative to its largest                        */
+  double estimable_tol;                /* 1e-3: largest null-vector component (unit vector, scaled coordinates) of an estimable slot */
+} lifcal_ba_covariance_options;
+
+typedef struct lifcal_ba_covariance_out {
+  double* camera;            /* [17 * 17] row-major, caller-allocated                                                                 */
+  double* pose;              /* [F * 36] or NULL: 6x6 block of every pose (order ax, ay, az, tx, ty, tz)                              */
+  double* pose_band;         /* [F * bw * 36] or NULL: S_ff^-1 blocks (j, j+dd), dd = 1..bw (bw: max_window_frames - 1), unscaled, gauge-relative */
+  double* camera_null;       /* [17 * 17] or NULL: first null_rank rows = camera components of the null directions (parameter units)  */
+  uint32_t estimable_mask;   /* bit j: camera slot j is live and estimable                                                            */
+  uint32_t null_rank;        /* null directions of C left after the gauge frame                                                       */
+  int32_t gauge_frame_used;  /* -1: none                                                                                              */
+  uint32_t live_mask;        /* bit j: camera slot j is a free parameter                                                              */
+  double sigma2;             /* 2 cost / (m - r), reported whether or not it was applied                                              */
+  double cost;               /* cost at the evaluated parameters                                                                      */
+  double seconds;            /* device time of the call (sweep + K1..K4)                                                              */
+} lifcal_ba_covariance_out;
+
+void lifcal_ba_default_covariance_options(lifcal_ba_covariance_options* o);
+int lifcal_ba_covariance(lifcal_ba_handle* h, const lifcal_ba_covariance_options* o, lifcal_ba_covariance_out* out);
+
 /* Poses held constant: fixed[f] != 0 keeps views[6f..6f+5] at their stored values in every following sweep / solve (ceres
  * SetParameterBlockConstant on that pose block: the frame's observations still constrain camera and points, its six columns
  * leave the reduced system).  fixed == NULL frees all poses again.  No reference counterpart; it is what the frame-windowed

@@ -73,6 +73,17 @@ class Profile(C.Structure):
                 ("ms_schur", C.c_double), ("ms_total", C.c_double), ("ms_exchange", C.c_double), ("n_sampled", C.c_uint32)]
 
 
+class CovarianceOptions(C.Structure):   # lifcal_ba_covariance_options
+    _fields_ = [("gauge_frame", C.c_int32), ("want_pose_blocks", C.c_int32), ("scale_by_residual_variance", C.c_int32),
+                ("reserved", C.c_int32), ("null_rcond", C.c_double), ("estimable_tol", C.c_double)]
+
+
+class CovarianceOut(C.Structure):       # lifcal_ba_covariance_out
+    _fields_ = [("camera", dptr), ("pose", dptr), ("pose_band", dptr), ("camera_null", dptr),
+                ("estimable_mask", C.c_uint32), ("null_rank", C.c_uint32), ("gauge_frame_used", C.c_int32), ("live_mask", C.c_uint32),
+                ("sigma2", C.c_double), ("cost", C.c_double), ("seconds", C.c_double)]
+
+
 class WindowReport(C.Structure):   # lifcal_ba_window_report
     _fields_ = [("first_frame", C.c_uint32), ("n_frames", C.c_uint32), ("n_fixed_frames", C.c_uint32), ("n_points", C.c_uint32), ("n_obs", C.c_uint32),
                 ("n_dropped_constraints", C.c_uint32), ("summary", Summary)]
@@ -220,6 +231,8 @@ PROTOTYPES = {
     "lifcal_ba_reproj_stats": (C.c_int, [C.c_void_p, C.c_double, C.POINTER(Stats)]),
     "lifcal_ba_project_observations": (C.c_int, [C.c_void_p, dptr, dptr]),
     "lifcal_ba_set_fixed_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)]),
+    "lifcal_ba_default_covariance_options": (None, [C.POINTER(CovarianceOptions)]),
+    "lifcal_ba_covariance": (C.c_int, [C.c_void_p, C.POINTER(CovarianceOptions), C.POINTER(CovarianceOut)]),
     "lifcal_ba_solve_windowed": (C.c_int, [C.POINTER(Problem), C.POINTER(Options), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(WindowReport), C.POINTER(C.c_uint32)]),
     "lifcal_ba_upload_parameters": (C.c_int, [C.c_void_p]),
     "lifcal_ba_download_parameters": (C.c_int, [C.c_void_p]),

@@ -10,6 +10,7 @@ There is no Python/CPU fallback: if the library is missing, loading raises.
 from __future__ import annotations
 
 import ctypes as C
+from dataclasses import dataclass
 from typing import Optional
 
 import numpy as np
@@ -41,6 +42,33 @@ class LifcalError(RuntimeError):
 def _check(lib, rc, what):
     if rc != 0:
         raise LifcalError(f"{what}: {lib.lifcal_ba_strerror(rc).decode()} ({rc}) {lib.lifcal_ba_last_error().decode()}")
+
+
+@dataclass
+class Covariance:
+    """Covariance of the calibrated parameters (BundleAdjustment.covariance, include/lifcal_ba.h lifcal_ba_covariance).
+
+    camera       17 x 17 block of G = H^- (Ceres units: unit-variance pixel residuals unless scaled by sigma2)
+    camera_std   sqrt of its diagonal; NaN where the slot is free but not determined by the data, 0 where it is fixed or absent
+    estimable    17 bools: free slots whose variance does not depend on the gauge / null-space choice
+    null_rank    null directions left after the gauge frame (e.g. the B / bL0 direction of an unconstrained scene)
+    camera_null  null_rank x 17: camera components of those directions, parameter units
+    poses        F x 6 x 6 blocks relative to the gauge frame, or None
+    gauge_frame  the frame held constant for the computation, or -1
+    sigma2       2 cost / (m - r): the residual variance estimate (an approximation under the Cauchy loss)
+    """
+    camera: np.ndarray
+    camera_std: np.ndarray
+    estimable: np.ndarray
+    null_rank: int
+    camera_null: np.ndarray
+    poses: Optional[np.ndarray]
+    gauge_frame: int
+    sigma2: float
+    live: np.ndarray
+    pose_band: Optional[np.ndarray] = None
+    seconds: float = 0.0
+    cost: float = 0.0
 
 
 class BundleAdjustment:
@@ -109,6 +137,35 @@ class BundleAdjustment:
             m = np.ascontiguousarray(fixed, np.uint8)
             assert len(m) == self.problem.struct.n_frames
             _check(self.lib, self.lib.lifcal_ba_set_fixed_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8))), "lifcal_ba_set_fixed_frames")
+
+    def covariance(self, gauge_frame: int = -1, want_pose_blocks: bool = True, scale_by_residual_variance: bool = False,
+                   null_rcond: Optional[float] = None, estimable_tol: Optional[float] = None, want_pose_band: bool = False) -> Covariance:
+        """Covariance of the parameters at the device-resident point (lifcal_ba_covariance); the handle is left as it was.
+        gauge_frame: -1 automatic (first observed frame when poses and points are both refined), >= 0 that frame, -2 none."""
+        o = capi.CovarianceOptions()
+        self.lib.lifcal_ba_default_covariance_options(C.byref(o))
+        o.gauge_frame = int(gauge_frame); o.want_pose_blocks = 1 if want_pose_blocks else 0
+        o.scale_by_residual_variance = 1 if scale_by_residual_variance else 0
+        if null_rcond is not None:
+            o.null_rcond = float(null_rcond)
+        if estimable_tol is not None:
+            o.estimable_tol = float(estimable_tol)
+        F = self.problem.struct.n_frames
+        cam = np.zeros((17, 17)); null = np.zeros((17, 17))
+        poses = np.zeros((F, 6, 6)) if want_pose_blocks else None
+        bw = self.info().max_window_frames - 1
+        band = np.zeros((F, bw, 6, 6)) if want_pose_band and bw > 0 else None
+        out = capi.CovarianceOut()
+        out.camera, out.camera_null = capi.as_dptr(cam), capi.as_dptr(null)
+        out.pose = capi.as_dptr(poses) if poses is not None else None
+        out.pose_band = capi.as_dptr(band) if band is not None else None
+        _check(self.lib, self.lib.lifcal_ba_covariance(self._h, C.byref(o), C.byref(out)), "lifcal_ba_covariance")
+        live = np.array([(out.live_mask >> j) & 1 for j in range(17)], bool)
+        est = np.array([(out.estimable_mask >> j) & 1 for j in range(17)], bool)
+        std = np.where(live, np.sqrt(np.maximum(np.diag(cam), 0.0)), 0.0)
+        std[live & ~est] = np.nan
+        return Covariance(cam, std, est, int(out.null_rank), null[: out.null_rank].copy(), poses, int(out.gauge_frame_used),
+                          float(out.sigma2), live, band, float(out.seconds), float(out.cost))
 
     # -- the benchmarked unit ------------------------------------------------------------------
     def sweep(self, radius: float = 1e4, want_matrices: bool = False):

@@ -1453,5 +1453,6 @@ __global__ __launch_bounds__(256) void k_stats(Dev d, TileSet ts, const CamConst
 
 }  // namespace lifcal
 #include "bandchol.hpp"   // single-wave LDS-window band Cholesky + back-substitution
+#include "covariance.hpp" // covariance of the parameters: chain without the arrow, selected inversion, multi-RHS back-substitution
 #include "bandchol2.hpp"  // the same as segment chains: twisted (two-ended) factorisation on two workgroups
 #include "bandchol3.hpp"  // block odd-even reduction over many workgroups (long sequences)
