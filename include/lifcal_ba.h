@@ -260,6 +260,22 @@ typedef struct lifcal_ba_covariance_out {
 void lifcal_ba_default_covariance_options(lifcal_ba_covariance_options* o);
 int lifcal_ba_covariance(lifcal_ba_handle* h, const lifcal_ba_covariance_options* o, lifcal_ba_covariance_out* out);
 
+/* ---- calibration judged in object space ----
+ * The numeric form of the reference's refCameraCoordinates / projectedCameraCoordinates folders (storeResults :1218-1287), at the
+ * device-resident parameters: for image points of the virtual image (x_v, y_v, virtual depth, frame, object point; host arrays)
+ * ref_c = RT P (:1256-1260) and proj_c = projectPointBack of the image point (:1276-1284, as include/lifcal_depth.h evaluates it:
+ * camera as stored, spx / spy of the problem), both [3n] host arrays or NULL.  The statistics are those of proj_c - ref_c over the
+ * points with vdepth >= 2 (the reference leaves smaller ones out of its initial fit, :482; they are counted in n_skipped),
+ * summed per workgroup and then over the workgroups in a fixed order: the result is reproducible.  One rank. */
+typedef struct lifcal_ba_object_space {
+  double rms[3];          /* sqrt(mean (proj_c - ref_c)^2) per axis     */
+  double max_abs[3];      /* largest |proj_c - ref_c| per axis          */
+  double rms_rel_depth;   /* RMS of (z_proj - z_ref) / z_ref            */
+  uint64_t n_used, n_skipped;
+} lifcal_ba_object_space;
+int lifcal_ba_object_space_stats(lifcal_ba_handle* h, uint64_t n, const double* x, const double* y, const double* vdepth, const uint32_t* fr,
+                                 const uint32_t* pt, double* ref_c, double* proj_c, lifcal_ba_object_space* out);
+
 /* Poses held constant: fixed[f] != 0 keeps views[6f..6f+5] at their stored values in every following sweep / solve (ceres
  * SetParameterBlockConstant on that pose block: the frame's observations still constrain camera and points, its six columns
  * leave the reduced system).  fixed == NULL frees all poses again.  No reference counterpart; it is what the frame-windowed

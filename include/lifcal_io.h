@@ -7,6 +7,9 @@
  *   storeExtrinsicOrientationsTxt  :1440-1481   ExtrinsicOrientations.txt  ("%05d" + 16 x " %16.10f", frames sorted by id)
  *   storeRawImagePointsCsv         :1483-1543   rawImagePoints.csv         ("%d,%d,%f,%f,%f,%f,%d")
  *   storeProtocol                  :1545-1617   calibrationProtocol.txt
+ *   storeResults                   :1131-1287   objectCoordinates.ply, objectCoordinatesWithCOLMAPIDs.txt, cameraOrientations.ply and the
+ *                                               per-frame clouds of refCameraCoordinates/ and projectedCameraCoordinates/ (numbers as
+ *                                               std::ofstream << double prints them: %g, six significant digits)
  * All functions return 0, LIFCAL_BA_ERR_INVALID_ARG (-1: null argument / file cannot be opened) or LIFCAL_BA_ERR_OUT_OF_RANGE (-4).
  */
 #ifndef LIFCAL_IO_H
@@ -44,6 +47,19 @@ typedef struct lifcal_protocol {
   double std_x, std_y, mae_x, mae_y;   /* lifcal_ba_stats */
 } lifcal_protocol;
 int lifcal_write_protocol(const char* path, const lifcal_protocol* p);
+
+/* objectCoordinates.ply (:1131-1144): the object points p3d_w, [3 n_points], each line "x y z 0" */
+int lifcal_write_object_coordinates_ply(const char* path, uint64_t n_points, const double* pts);
+/* objectCoordinatesWithCOLMAPIDs.txt (:1146-1152): "id x y z" per point, colmap_ids[i] = getCorrespondingCOLMAPID of point i */
+int lifcal_write_object_coordinates_colmap_ids(const char* path, uint64_t n_points, const int32_t* colmap_ids, const double* pts);
+/* cameraOrientations.ply (:1154-1216): per frame the projection centre and the four image corners at three focal lengths, moved to
+ * world coordinates by the inverse pose, and four triangles.  The frustum is built in float as the reference builds it (:1170-1180)
+ * from c (cx, cy), fL and pixelSize_totFoc. */
+int lifcal_write_camera_orientations_ply(const char* path, uint32_t n_frames, const double* views, int32_t image_width, int32_t image_height,
+                                         double cx, double cy, double fL, double pixel_size_tot_foc);
+/* <dir>/cameraCoordinates_%04d.ply of one frame (:1244-1286), frame_id = frame.id: serves refCameraCoordinates/ (ref_c of
+ * lifcal_ba_object_space_stats) and projectedCameraCoordinates/ (proj_c); xyz: [3 n_points] of the frame.  The directory must exist. */
+int lifcal_write_camera_coordinates_ply(const char* dir, int32_t frame_id, uint64_t n_points, const double* xyz);
 
 #ifdef __cplusplus
 }

@@ -7,3 +7,4 @@ from . import _capi, scene  # noqa: F401
 from .bundle_adjustment import (BundleAdjustment, Covariance, LifcalError, make_config, plan, comm_unique_id, initPlenopticParameters,  # noqa: F401
                                 performBundleAdjustmentWindowed)
 from .mla import MicroLensGrid, RawObservations  # noqa: F401
+from .depth import DepthMaps, backProjectPoints, readDepthData, read_png16, depth_is_estimable  # noqa: F401

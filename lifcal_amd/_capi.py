@@ -199,6 +199,10 @@ IO_PROTOTYPES = {
     "lifcal_write_extrinsic_orientations_txt": (C.c_int, [C.c_char_p, C.c_uint32, _iptr, dptr]),
     "lifcal_write_raw_image_points_csv": (C.c_int, [C.c_char_p, C.c_uint64, C.c_uint32, _iptr, uptr, dptr, dptr, dptr, dptr, uptr]),
     "lifcal_write_protocol": (C.c_int, [C.c_char_p, C.POINTER(Protocol)]),
+    "lifcal_write_object_coordinates_ply": (C.c_int, [C.c_char_p, C.c_uint64, dptr]),
+    "lifcal_write_object_coordinates_colmap_ids": (C.c_int, [C.c_char_p, C.c_uint64, _iptr, dptr]),
+    "lifcal_write_camera_orientations_ply": (C.c_int, [C.c_char_p, C.c_uint32, dptr, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]),
+    "lifcal_write_camera_coordinates_ply": (C.c_int, [C.c_char_p, C.c_int32, C.c_uint64, dptr]),
 }
 
 class ColmapInfo(C.Structure):     # include/lifcal_colmap.h lifcal_colmap_info
@@ -218,6 +222,39 @@ COLMAP_PROTOTYPES = {
     "lifcal_colmap_free": (None, [C.c_void_p]),
 }
 
+class ObjectSpace(C.Structure):      # include/lifcal_ba.h lifcal_ba_object_space
+    _fields_ = [("rms", C.c_double * 3), ("max_abs", C.c_double * 3), ("rms_rel_depth", C.c_double), ("n_used", C.c_uint64), ("n_skipped", C.c_uint64)]
+
+
+class DepthSampleCounts(C.Structure):   # include/lifcal_depth.h lifcal_depth_sample_counts
+    _fields_ = [("direct", C.c_uint64), ("interpolated", C.c_uint64), ("failed", C.c_uint64)]
+
+
+class DepthCamera(C.Structure):      # lifcal_depth_camera
+    _fields_ = [("cam", C.c_double * 17), ("spx", C.c_double), ("spy", C.c_double), ("config", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class DepthPoints(C.Structure):      # lifcal_depth_points
+    _fields_ = [("n", C.c_uint64), ("x", dptr), ("y", dptr), ("vdepth", dptr), ("fr", uptr), ("views", dptr), ("n_frames", C.c_uint32), ("reserved", C.c_uint32),
+                ("cam_cov", dptr), ("sigma_v", C.c_double), ("p_c", dptr), ("p_w", dptr), ("jac", dptr), ("dpc_dv", dptr), ("cov_pc", dptr), ("n_invalid", C.c_uint64)]
+
+
+class DepthMapsArgs(C.Structure):    # lifcal_depth_maps
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("eval", C.c_int32), ("out_double", C.c_int32), ("out_on_device", C.c_int32), ("n_frames", C.c_uint32),
+                ("frame", uptr), ("views", dptr), ("cam_cov", dptr), ("sigma_v", C.c_double), ("xyz", C.c_void_p), ("z", C.c_void_p), ("sigma_z", C.c_void_p),
+                ("n_invalid", C.c_uint64), ("seconds", C.c_double)]
+
+
+# every symbol include/lifcal_depth.h declares
+DEPTH_PROTOTYPES = {
+    "lifcal_depth_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
+    "lifcal_depth_destroy": (None, [C.c_void_p]),
+    "lifcal_depth_set_maps": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_int32]),
+    "lifcal_depth_sample": (C.c_int, [C.c_void_p, C.c_uint64, dptr, dptr, _iptr, dptr, C.POINTER(DepthSampleCounts)]),
+    "lifcal_depth_back_project_points": (C.c_int, [C.c_int32, C.POINTER(DepthCamera), C.POINTER(DepthPoints)]),
+    "lifcal_depth_back_project_maps": (C.c_int, [C.c_void_p, C.POINTER(DepthCamera), C.POINTER(DepthMapsArgs)]),
+}
+
 # every symbol include/lifcal_ba.h declares: name -> (restype, argtypes)
 PROTOTYPES = {
     "lifcal_ba_default_options": (None, [C.POINTER(Options)]),
@@ -233,6 +270,7 @@ PROTOTYPES = {
     "lifcal_ba_set_fixed_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)]),
     "lifcal_ba_default_covariance_options": (None, [C.POINTER(CovarianceOptions)]),
     "lifcal_ba_covariance": (C.c_int, [C.c_void_p, C.POINTER(CovarianceOptions), C.POINTER(CovarianceOut)]),
+    "lifcal_ba_object_space_stats": (C.c_int, [C.c_void_p, C.c_uint64, dptr, dptr, dptr, uptr, uptr, dptr, dptr, C.POINTER(ObjectSpace)]),
     "lifcal_ba_solve_windowed": (C.c_int, [C.POINTER(Problem), C.POINTER(Options), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(WindowReport), C.POINTER(C.c_uint32)]),
     "lifcal_ba_upload_parameters": (C.c_int, [C.c_void_p]),
     "lifcal_ba_download_parameters": (C.c_int, [C.c_void_p]),
@@ -266,7 +304,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

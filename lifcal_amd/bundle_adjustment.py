@@ -41,7 +41,9 @@ class LifcalError(RuntimeError):
 
 def _check(lib, rc, what):
     if rc != 0:
-        raise LifcalError(f"{what}: {lib.lifcal_ba_strerror(rc).decode()} ({rc}) {lib.lifcal_ba_last_error().decode()}")
+        err = LifcalError(f"{what}: {lib.lifcal_ba_strerror(rc).decode()} ({rc}) {lib.lifcal_ba_last_error().decode()}")
+        err.code = rc   # the lifcal_ba_status value
+        raise err
 
 
 @dataclass
@@ -166,6 +168,23 @@ class BundleAdjustment:
         std[live & ~est] = np.nan
         return Covariance(cam, std, est, int(out.null_rank), null[: out.null_rank].copy(), poses, int(out.gauge_frame_used),
                           float(out.sigma2), live, band, float(out.seconds), float(out.cost))
+
+    def objectSpaceStats(self, x, y, vdepth, fr, pt):
+        """The calibration judged in object space at the device-resident parameters (lifcal_ba_object_space_stats): for image
+        points of the virtual image (x_v, y_v, virtual depth, frame, object point) returns (stats, ref_c, proj_c) with
+        ref_c = RT P (reference storeResults :1256-1260) and proj_c = projectPointBack of the image point (:1276-1284), both (n, 3),
+        and stats.rms / .max_abs per axis of proj_c - ref_c, .rms_rel_depth, .n_used, .n_skipped (vdepth < 2)."""
+        x = np.ascontiguousarray(x, np.float64).reshape(-1); y = np.ascontiguousarray(y, np.float64).reshape(-1)
+        vd = np.ascontiguousarray(vdepth, np.float64).reshape(-1)
+        fr = np.ascontiguousarray(fr, np.uint32).reshape(-1); pt = np.ascontiguousarray(pt, np.uint32).reshape(-1)
+        n = len(x)
+        if not (len(y) == len(vd) == len(fr) == len(pt) == n):
+            raise LifcalError("objectSpaceStats: arrays differ in length")
+        ref = np.zeros((n, 3)); proj = np.zeros((n, 3))
+        st = capi.ObjectSpace()
+        _check(self.lib, self.lib.lifcal_ba_object_space_stats(self._h, n, capi.as_dptr(x), capi.as_dptr(y), capi.as_dptr(vd), capi.as_uptr(fr), capi.as_uptr(pt),
+                                                               capi.as_dptr(ref), capi.as_dptr(proj), C.byref(st)), "lifcal_ba_object_space_stats")
+        return st, ref, proj
 
     # -- the benchmarked unit ------------------------------------------------------------------
     def sweep(self, radius: float = 1e4, want_matrices: bool = False):

@@ -436,7 +436,7 @@ LIFCAL_DEV double finalize_column(const Dev& d, uint32_t t, double radius) {
 }  // namespace lifcal
 #include "sweep2.hpp"   // k_sweep2: the LDS-window fused sweep (regular points)
 #include "sweep3.hpp"   // k_sweep3: the same with a wave-specialised observation loop (512 threads)
-#include "sweep4.hpp"   // k_front4 + k_back4: the sweep cut in two kernels built for occupancy (default)
+#include "sweep4.hpp"   // k_front4 + k_back4: the sweep cut in two kernels built for occupancy (LIFCAL_SWEEP_KERNEL=4 only; k_sweep3 is the default)
 namespace lifcal {
 
 // ---------------------------------------------------------------------------------------------

@@ -1694,3 +1694,6 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 
 // frame-windowed solve for long sequences (include/lifcal_ba.h)
 #include "windowed.hpp"
+
+// depth-map sampling, back-projection to metric 3D and the object-space comparison (include/lifcal_depth.h, include/lifcal_ba.h)
+#include "depth.hpp"

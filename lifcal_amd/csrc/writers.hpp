@@ -1,6 +1,7 @@
 // writers.hpp — LiFCal's result files (include/lifcal_io.h).  Host code only; included at the end of lifcal_ba.hip.
 // The two XML files follow pugixml's default output (declaration, tab indentation, text-only elements on one line) and
-// boost::lexical_cast<std::string>(double), which prints 17 significant digits in %g style.
+// boost::lexical_cast<std::string>(double), which prints 17 significant digits in %g style.  The point clouds are written with
+// std::ofstream << double, i.e. %g with six significant digits.
 #pragma once
 #include <algorithm>
 #include <cstdio>
@@ -35,6 +36,15 @@ inline void rigid_matrix(const double* a, const double* t, double m[4][4]) {
                           {-cx * sy * cz + sx * sz, cx * sy * sz + sx * cz, cx * cy}};
   for (int i = 0; i < 4; ++i) for (int j = 0; j < 4; ++j) m[i][j] = i == j ? 1.0 : 0.0;
   for (int i = 0; i < 3; ++i) { for (int j = 0; j < 3; ++j) m[i][j] = R[i][j]; m[i][3] = t[i]; }
+}
+
+// the vertex list the reference's point-cloud files share (src/CameraCalibration.cpp:1134-1143, :1245-1260): x y z and a zero intensity
+inline int write_cloud_ply(const char* path, uint64_t n, const double* xyz) {
+  FILE* f = std::fopen(path, "w");
+  if (!f) return LIFCAL_BA_ERR_INVALID_ARG;
+  std::fprintf(f, "ply\nformat ascii 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\nproperty uchar intensity\nend_header\n", (unsigned long long)n);
+  for (uint64_t i = 0; i < n; ++i) std::fprintf(f, "%g %g %g 0\n", xyz[3 * i], xyz[3 * i + 1], xyz[3 * i + 2]);
+  return std::fclose(f) == 0 ? 0 : LIFCAL_BA_ERR_INVALID_ARG;
 }
 
 }  // namespace lifcal_io
@@ -155,6 +165,62 @@ int lifcal_write_protocol(const char* path, const lifcal_protocol* p) {
   std::fprintf(f, "\tmae x:                 %8.5f\n", p->mae_x);
   std::fprintf(f, "\tmae y:                 %8.5f\n", p->mae_y);
   return std::fclose(f) == 0 ? 0 : LIFCAL_BA_ERR_INVALID_ARG;
+}
+
+int lifcal_write_object_coordinates_ply(const char* path, uint64_t n_points, const double* pts) {
+  if (!path || (n_points && !pts)) return LIFCAL_BA_ERR_INVALID_ARG;
+  return lifcal_io::write_cloud_ply(path, n_points, pts);
+}
+
+int lifcal_write_object_coordinates_colmap_ids(const char* path, uint64_t n_points, const int32_t* colmap_ids, const double* pts) {
+  if (!path || (n_points && (!colmap_ids || !pts))) return LIFCAL_BA_ERR_INVALID_ARG;
+  FILE* f = std::fopen(path, "w");
+  if (!f) return LIFCAL_BA_ERR_INVALID_ARG;
+  std::fprintf(f, "# COLMAP_ID X Y Z\n");
+  for (uint64_t i = 0; i < n_points; ++i) std::fprintf(f, "%d %g %g %g\n", colmap_ids[i], pts[3 * i], pts[3 * i + 1], pts[3 * i + 2]);
+  return std::fclose(f) == 0 ? 0 : LIFCAL_BA_ERR_INVALID_ARG;
+}
+
+int lifcal_write_camera_orientations_ply(const char* path, uint32_t n_frames, const double* views, int32_t image_width, int32_t image_height,
+                                         double cx_d, double cy_d, double fL_d, double pixel_size_tot_foc) {
+#pragma clang fp contract(off)
+  if (!path || (n_frames && !views)) return LIFCAL_BA_ERR_INVALID_ARG;
+  FILE* fp = std::fopen(path, "w");
+  if (!fp) return LIFCAL_BA_ERR_INVALID_ARG;
+  std::fprintf(fp, "ply\nformat ascii 1.0\nelement vertex %llu\nproperty float x\nproperty float y\nproperty float z\n"
+                   "property uchar red\nproperty uchar green\nproperty uchar blue\nelement face %llu\nproperty list uchar int vertex_index\nend_header\n",
+               (unsigned long long)n_frames * 5, (unsigned long long)n_frames * 4);
+  // the frustum in float, as the reference builds it (:1170-1180): image corners at three focal lengths
+  const float cx = (float)cx_d, cy = (float)cy_d;
+  const float f = (float)(fL_d / pixel_size_tot_foc);
+  const float fL = (float)(fL_d * 3);
+  const float w = (float)image_width, h = (float)image_height;
+  const double v[5][3] = {{0, 0, 0},
+                          {(0 - cx) / f * fL, (0 - cy) / f * fL, fL},
+                          {(0 - cx) / f * fL, (h - 1 - cy) / f * fL, fL},
+                          {(w - 1 - cx) / f * fL, (h - 1 - cy) / f * fL, fL},
+                          {(w - 1 - cx) / f * fL, (0 - cy) / f * fL, fL}};
+  for (uint32_t i = 0; i < n_frames; ++i) {
+    double m[4][4];
+    lifcal_io::rigid_matrix(views + 6 * (size_t)i, views + 6 * (size_t)i + 3, m);
+    for (int k = 0; k < 5; ++k) {   // camera to world: R^T (v - t), the inverse of the rigid transform
+      double o[3];
+      for (int r = 0; r < 3; ++r) o[r] = m[0][r] * (v[k][0] - m[0][3]) + m[1][r] * (v[k][1] - m[1][3]) + m[2][r] * (v[k][2] - m[2][3]);
+      std::fprintf(fp, "%g %g %g 0 0 255\n", o[0], o[1], o[2]);
+    }
+  }
+  for (uint32_t i = 0; i < n_frames; ++i) {
+    const unsigned long long b = (unsigned long long)i * 5;
+    std::fprintf(fp, "3 %llu %llu %llu\n3 %llu %llu %llu\n3 %llu %llu %llu\n3 %llu %llu %llu\n", b, b + 1, b + 2, b, b + 2, b + 3, b, b + 3, b + 4, b, b + 4, b + 1);
+  }
+  return std::fclose(fp) == 0 ? 0 : LIFCAL_BA_ERR_INVALID_ARG;
+}
+
+int lifcal_write_camera_coordinates_ply(const char* dir, int32_t frame_id, uint64_t n_points, const double* xyz) {
+  if (!dir || (n_points && !xyz)) return LIFCAL_BA_ERR_INVALID_ARG;
+  char name[64];
+  std::snprintf(name, sizeof name, "/cameraCoordinates_%04d.ply", frame_id);
+  return lifcal_io::write_cloud_ply((std::string(dir) + name).c_str(), n_points, xyz);
 }
 
 }  // extern "C"

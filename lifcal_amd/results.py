@@ -1,4 +1,4 @@
-"""Host mirror of the reference's result writers (CameraCalibration::store*, src/CameraCalibration.cpp:1296-1617) over
+"""Host mirror of the reference's result writers (CameraCalibration::store*, src/CameraCalibration.cpp:1131-1287, :1296-1617) over
 include/lifcal_io.h.  Host code inside liblifcal_ba.so; no GPU needed."""
 from __future__ import annotations
 
@@ -67,3 +67,40 @@ def storeProtocol(dir_results: str, model: capi.CameraModel, config: int, stats)
     p.robust_cost = 1 if config & 0x200 else 0
     p.std_x, p.std_y, p.mae_x, p.mae_y = stats.std_x, stats.std_y, stats.mae_x, stats.mae_y
     _ok(capi.load_library().lifcal_write_protocol(os.path.join(dir_results, "calibrationProtocol.txt").encode(), C.byref(p)), "storeProtocol")
+
+
+def storeObjectCoordinates(dir_results: str, pts):
+    """objectCoordinates.ply (:1131-1144)"""
+    p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3)
+    _ok(capi.load_library().lifcal_write_object_coordinates_ply(os.path.join(dir_results, "objectCoordinates.ply").encode(), len(p), capi.as_dptr(p)), "storeObjectCoordinates")
+
+
+def storeObjectCoordinatesWithCOLMAPIDs(dir_results: str, colmap_ids, pts):
+    """objectCoordinatesWithCOLMAPIDs.txt (:1146-1152)"""
+    p = np.ascontiguousarray(pts, np.float64).reshape(-1, 3); ids = np.ascontiguousarray(colmap_ids, np.int32).reshape(-1)
+    if len(ids) != len(p):
+        raise LifcalError("storeObjectCoordinatesWithCOLMAPIDs: one id per point")
+    _ok(capi.load_library().lifcal_write_object_coordinates_colmap_ids(os.path.join(dir_results, "objectCoordinatesWithCOLMAPIDs.txt").encode(), len(p),
+                                                                       ids.ctypes.data_as(capi._iptr), capi.as_dptr(p)), "storeObjectCoordinatesWithCOLMAPIDs")
+
+
+def storeCameraOrientationsPly(dir_results: str, views, image_size: Sequence[int], camera: Sequence[float], pixel_size_tot_foc: float):
+    """cameraOrientations.ply (:1154-1216): one frustum per frame, for viewing the poses next to the point cloud"""
+    v = np.ascontiguousarray(views, np.float64).reshape(-1)
+    _ok(capi.load_library().lifcal_write_camera_orientations_ply(os.path.join(dir_results, "cameraOrientations.ply").encode(), len(v) // 6, capi.as_dptr(v),
+                                                                 int(image_size[0]), int(image_size[1]), float(camera[3]), float(camera[4]), float(camera[0]),
+                                                                 float(pixel_size_tot_foc)), "storeCameraOrientationsPly")
+
+
+def storeCameraCoordinates(dir_results: str, folder: str, frame_ids, fr, xyz):
+    """<dir_results>/<folder>/cameraCoordinates_%04d.ply, one file per frame (:1218-1287).  folder: "refCameraCoordinates" with
+    ref_c of BundleAdjustment.objectSpaceStats, "projectedCameraCoordinates" with proj_c; fr: frame index per point."""
+    d = os.path.join(dir_results, folder)
+    os.makedirs(d, exist_ok=True)
+    fr = np.asarray(fr).reshape(-1); p = np.asarray(xyz, np.float64).reshape(-1, 3)
+    if len(fr) != len(p):
+        raise LifcalError("storeCameraCoordinates: one frame index per point")
+    lib = capi.load_library()
+    for f, fid in enumerate(np.asarray(frame_ids).reshape(-1)):
+        sel = np.ascontiguousarray(p[fr == f])
+        _ok(lib.lifcal_write_camera_coordinates_ply(d.encode(), int(fid), len(sel), capi.as_dptr(sel)), "storeCameraCoordinates")
