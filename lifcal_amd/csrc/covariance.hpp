@@ -1,4 +1,5 @@
-// covariance.hpp — device side of lifcal_ba_covariance (included by kernels.hpp after bandchol.hpp).  DESIGN.md section 7h.
+// covariance.hpp — lifcal_ba_covariance: its kernels, then its host driver (included at the end of lifcal_ba.hip, behind the handle
+// and the launch helpers the driver uses).  DESIGN.md section 7h.
 //
 // H = [S_ff S_fa; S_af S_aa] is the UNDAMPED reduced system of the sweep at radius = infinity (poses f | arrow a = promoted
 // points + camera slots).  With S_ff = L_ff L_ff^T, C = S_aa - S_af S_ff^-1 S_fa and Y = S_ff^-1 S_fa = L_ff^-T L_af^T, a
@@ -364,3 +365,203 @@ __global__ __launch_bounds__(64) void k_cov_combine(Dev d, const double* Zd, con
 }
 
 }  // namespace lifcal
+
+// ---- host side ----  symmetric eigen-decomposition of a small n x n matrix (cyclic Jacobi, fixed sweep order: deterministic): A row-major, destroyed;
+// w[i] eigenvalues, V[r * n + i] the unit eigenvector of w[i] in column i
+static void sym_eig_jacobi(uint32_t n, std::vector<double>& A, std::vector<double>& w, std::vector<double>& V) {
+  V.assign((size_t)n * n, 0.0);
+  for (uint32_t i = 0; i < n; ++i) V[(size_t)i * n + i] = 1.0;
+  for (int sweep = 0; sweep < 100; ++sweep) {
+    double off = 0.0, tot = 0.0;
+    for (uint32_t p = 0; p < n; ++p)
+      for (uint32_t q = 0; q < n; ++q) { const double v = A[(size_t)p * n + q] * A[(size_t)p * n + q]; tot += v; if (p != q) off += v; }
+    if (off <= 1e-34 * tot || off == 0.0) break;
+    for (uint32_t p = 0; p + 1 < n; ++p)
+      for (uint32_t q = p + 1; q < n; ++q) {
+        const double apq = A[(size_t)p * n + q];
+        if (apq == 0.0) continue;
+        const double app = A[(size_t)p * n + p], aqq = A[(size_t)q * n + q];
+        const double theta = (aqq - app) / (2.0 * apq);
+        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
+        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
+        for (uint32_t k = 0; k < n; ++k) {   // A <- A J (columns p, q)
+          const double akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
+          A[(size_t)k * n + p] = c * akp - sn * akq; A[(size_t)k * n + q] = sn * akp + c * akq;
+        }
+        for (uint32_t k = 0; k < n; ++k) {   // A <- J^T A (rows p, q)
+          const double apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
+          A[(size_t)p * n + k] = c * apk - sn * aqk; A[(size_t)q * n + k] = sn * apk + c * aqk;
+        }
+        A[(size_t)p * n + q] = 0.0; A[(size_t)q * n + p] = 0.0;
+        for (uint32_t k = 0; k < n; ++k) {
+          const double vkp = V[(size_t)k * n + p], vkq = V[(size_t)k * n + q];
+          V[(size_t)k * n + p] = c * vkp - sn * vkq; V[(size_t)k * n + q] = sn * vkp + c * vkq;
+        }
+      }
+  }
+  w.resize(n);
+  for (uint32_t i = 0; i < n; ++i) w[i] = A[(size_t)i * n + i];
+}
+
+extern "C" void lifcal_ba_default_covariance_options(lifcal_ba_covariance_options* o) {
+  if (!o) return;
+  o->gauge_frame = -1; o->want_pose_blocks = 1; o->scale_by_residual_variance = 0; o->reserved = 0;
+  o->null_rcond = 1e-9; o->estimable_tol = 1e-3;
+}
+
+// sweep at radius = infinity (no damping anywhere: clamp(..) / (inf s^2) = 0, on the point blocks U_p too),
+// K1 chain -> C, K2 / K3 on the factor, C+ on the host, K4.  The handle's state is put back before returning, on every path.
+extern "C" int lifcal_ba_covariance(lifcal_ba_handle* h, const lifcal_ba_covariance_options* oin, lifcal_ba_covariance_out* out) {
+  if (!h || !out || !out->camera) { g_last_error = "lifcal_ba_covariance: null handle, output or output->camera"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  lifcal_ba_covariance_options o; if (oin) o = *oin; else lifcal_ba_default_covariance_options(&o);
+  Dev& d = h->d;
+  const uint32_t F = d.F, NA = d.NA, Q3 = 3 * d.Q, nc = d.nc;
+  if (h->opt.world_size > 1) { g_last_error = "lifcal_ba_covariance: world_size > 1 is not supported (every rank holds the reduced system: a follow-up)"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  if (h->opt.precision != 0) { g_last_error = "lifcal_ba_covariance: options.precision = 1 is not supported; create a second fp64 handle at the solved parameters"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  if (!h->use_sweep3 || h->use_sweep4) { g_last_error = "lifcal_ba_covariance needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  const size_t lds2 = (size_t)cov_selinv_lds(d.bw) * 8, lds3 = (size_t)cov_backsolve_lds(d.bw, NA) * 8, lds4 = (size_t)6 * NA * 8;
+  if (!h->bandw_ok || lds2 > 160 * 1024 || lds3 > 160 * 1024 || lds4 > 64 * 1024) {
+    g_last_error = "lifcal_ba_covariance: the band window (" + std::to_string(d.bw + 1) + " frames, " + std::to_string(NA) + " arrow rows) does not fit LDS; only the LDS-window factorisation is supported";
+    return LIFCAL_BA_ERR_INVALID_ARG;
+  }
+  if (!(o.null_rcond >= 0.0) || !(o.estimable_tol >= 0.0) || o.gauge_frame < -2 || (o.gauge_frame >= 0 && (uint32_t)o.gauge_frame >= F)) {
+    g_last_error = "lifcal_ba_covariance: gauge_frame must be -2, -1 or a frame index; null_rcond and estimable_tol >= 0"; return LIFCAL_BA_ERR_INVALID_ARG;
+  }
+  // the gauge frame: held constant for this call only
+  const std::vector<uint8_t> live_saved = h->frame_live_host;
+  bool any_fixed = false;
+  for (uint32_t f = 0; f < F; ++f) if (h->plan.frame_used[f] && !live_saved[f]) any_fixed = true;
+  int32_t gauge = -1;
+  if (o.gauge_frame >= 0) {
+    if (!d.use_poses || !live_saved[o.gauge_frame]) { g_last_error = "lifcal_ba_covariance: the gauge frame must be an observed frame whose pose is refined"; return LIFCAL_BA_ERR_INVALID_ARG; }
+    gauge = o.gauge_frame;
+  } else if (o.gauge_frame == -1 && d.use_poses && d.use_points && !any_fixed) {
+    for (uint32_t f = 0; f < F; ++f) if (live_saved[f]) { gauge = (int32_t)f; break; }
+  }
+  HIP_TRY(hipSetDevice(h->opt.device));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  HIP_TRY(hipFuncSetAttribute((const void*)k_cov_chol_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bandw_lds));
+  HIP_TRY(hipFuncSetAttribute((const void*)k_cov_selinv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
+  HIP_TRY(hipFuncSetAttribute((const void*)k_cov_backsolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
+#define CA(ptr, n) do { if (!(ptr)) { if (int rc_ = dev_alloc(h, &(ptr), (n))) return rc_; } } while (0)
+  CA(h->cov_C, (size_t)NA * NA); CA(h->cov_Cp, (size_t)NA * NA); CA(h->cov_Zd, (size_t)std::max(1u, F) * 36); CA(h->cov_Y, (size_t)std::max(1u, F) * 6 * NA);
+  CA(h->cov_G, (size_t)std::max(1u, F) * 36); CA(h->cov_fail, 1);
+  if (out->pose_band && d.bw) CA(h->cov_Zb, (size_t)std::max(1u, F) * d.bw * 36);
+#undef CA
+  // what the call changes and puts back: the frame mask, the Jacobi scaling state, the device LM state, the profile span
+  const bool sigma_saved = h->sigma_valid, prof_saved = h->prof_on;
+  double lm_saved[LM_N];
+  HIP_TRY(hipMemcpy(lm_saved, d.lm, sizeof(lm_saved), hipMemcpyDeviceToHost));
+  auto restore = [&]() -> int {
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (F) HIP_TRY(hipMemcpy(h->frame_live_dev, live_saved.data(), F, hipMemcpyHostToDevice));
+    HIP_TRY(hipMemcpy(d.lm, lm_saved, sizeof(lm_saved), hipMemcpyHostToDevice));
+    h->sigma_valid = sigma_saved; h->prof_on = prof_saved;
+    return 0;
+  };
+  auto bail = [&](int rc) { const std::string e = g_last_error; restore(); g_last_error = e; return rc; };
+  h->prof_on = false;
+  if (gauge >= 0) {
+    std::vector<uint8_t> live(live_saved); live[gauge] = 0;
+    if (hipMemcpy(h->frame_live_dev, live.data(), F, hipMemcpyHostToDevice) != hipSuccess) { g_last_error = "lifcal_ba_covariance: frame mask upload failed"; return bail(LIFCAL_BA_ERR_HIP); }
+  }
+  // ---- the undamped reduced system, K1 .. K3 ----
+  if (hipEventRecord(h->ev0, h->stream) != hipSuccess) { g_last_error = "hipEventRecord failed"; return bail(LIFCAL_BA_ERR_HIP); }
+  if (int rc = launch_sweep(h, std::numeric_limits<double>::infinity())) return bail(rc);
+  hipLaunchKernelGGL(k_cov_chol_w, dim3(1), dim3(256), h->bandw_lds, h->stream, d, h->Lpanel, h->cov_C, h->cov_fail);
+  hipLaunchKernelGGL(k_cov_backsolve, dim3(1), dim3(256), lds3, h->stream, d, (const double*)h->Lpanel, h->cov_Y);
+  const bool want_pose = d.use_poses && (o.want_pose_blocks || out->pose_band);
+  if (want_pose) hipLaunchKernelGGL(k_cov_selinv, dim3(1), dim3(256), lds2, h->stream, d, (const double*)h->Lpanel, h->cov_Zd, out->pose_band && d.bw ? h->cov_Zb : nullptr);
+  if (hipGetLastError() != hipSuccess) { g_last_error = "lifcal_ba_covariance: kernel launch failed"; return bail(LIFCAL_BA_ERR_HIP); }
+  double cost, gmax, bad;
+  if (int rc = read_sweep_scalars(h, &cost, &gmax, &bad)) return bail(rc);
+  std::vector<double> C((size_t)NA * NA);
+  double failv = 0.0;
+  if (hipMemcpy(C.data(), h->cov_C, C.size() * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&failv, h->cov_fail, 8, hipMemcpyDeviceToHost) != hipSuccess) {
+    g_last_error = "lifcal_ba_covariance: read-back failed"; return bail(LIFCAL_BA_ERR_HIP);
+  }
+  if (!std::isfinite(cost)) { g_last_error = "lifcal_ba_covariance: non-finite cost at the stored parameters"; return bail(LIFCAL_BA_ERR_NUMERIC); }
+  if (failv != 0.0) {
+    g_last_error = "lifcal_ba_covariance: the pose block of frame " + std::to_string((long long)failv - 1) + " is not positive definite after elimination: the data do not pin that frame down";
+    return bail(LIFCAL_BA_ERR_NUMERIC);
+  }
+  // ---- C+ on the live arrow slots (promoted points, free camera slots), Jacobi-scaled ----
+  CamConsts cc;
+  if (hipMemcpy(&cc, d.camc, sizeof(cc), hipMemcpyDeviceToHost) != hipSuccess) { g_last_error = "lifcal_ba_covariance: read-back failed"; return bail(LIFCAL_BA_ERR_HIP); }
+  std::vector<uint32_t> la;   // live arrow rows
+  for (uint32_t a = 0; a < NA; ++a) if (a < Q3 || cc.chm[a - Q3] != 0.0) la.push_back(a);
+  const uint32_t n = (uint32_t)la.size();
+  std::vector<double> sc(n), Cs((size_t)n * n), w, V;
+  for (uint32_t i = 0; i < n; ++i) { const double c = C[(size_t)la[i] * NA + la[i]]; sc[i] = c > 0.0 ? 1.0 / std::sqrt(c) : 1.0; }
+  for (uint32_t i = 0; i < n; ++i)
+    for (uint32_t k = 0; k < n; ++k) Cs[(size_t)i * n + k] = 0.5 * (C[(size_t)la[i] * NA + la[k]] + C[(size_t)la[k] * NA + la[i]]) * sc[i] * sc[k];
+  sym_eig_jacobi(n, Cs, w, V);
+  double wmax = 0.0;
+  for (double x : w) wmax = std::max(wmax, x);
+  std::vector<uint32_t> nulls;
+  for (uint32_t i = 0; i < n; ++i) if (!(w[i] > o.null_rcond * wmax)) nulls.push_back(i);
+  std::sort(nulls.begin(), nulls.end(), [&](uint32_t x, uint32_t y) { return w[x] < w[y]; });
+  std::vector<double> Cp((size_t)NA * NA, 0.0);
+  for (uint32_t i = 0; i < n; ++i)
+    for (uint32_t k = 0; k < n; ++k) {
+      double s = 0.0;
+      for (uint32_t e = 0; e < n; ++e) if (w[e] > o.null_rcond * wmax) s += V[(size_t)i * n + e] * V[(size_t)k * n + e] / w[e];
+      Cp[(size_t)la[i] * NA + la[k]] = s * sc[i] * sc[k];
+    }
+  // ---- units: residual variance over the rank of H ----
+  uint64_t n_free = 0, n_pts = 0;
+  for (uint32_t f = 0; f < F; ++f) if (d.use_poses && live_saved[f]) n_free += 6;
+  if (d.use_points) for (uint32_t q = 0; q < d.P; ++q) if (h->plan.point_used[q]) ++n_pts;
+  n_free += 3 * n_pts;
+  uint32_t live_mask = 0;
+  for (uint32_t j = 0; j < nc; ++j) if (cc.chm[j] != 0.0) { live_mask |= 1u << j; ++n_free; }
+  const uint64_t m = 2 * (uint64_t)h->plan.n_obs_local + d.M_local;
+  const double r = (double)n_free - (gauge >= 0 ? 6.0 : 0.0) - (double)nulls.size();
+  const double sigma2 = (double)m > r ? 2.0 * cost / ((double)m - r) : std::numeric_limits<double>::quiet_NaN();
+  const double mult = o.scale_by_residual_variance ? sigma2 : 1.0;
+  // ---- K4 ----
+  if (want_pose && o.want_pose_blocks && out->pose) {
+    if (hipMemcpyAsync(h->cov_Cp, Cp.data(), Cp.size() * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) { g_last_error = "lifcal_ba_covariance: upload failed"; return bail(LIFCAL_BA_ERR_HIP); }
+    hipLaunchKernelGGL(k_cov_combine, dim3(F), dim3(64), lds4, h->stream, d, (const double*)h->cov_Zd, (const double*)h->cov_Y, (const double*)h->cov_Cp, mult, h->cov_G);
+    if (hipGetLastError() != hipSuccess) { g_last_error = "lifcal_ba_covariance: kernel launch failed"; return bail(LIFCAL_BA_ERR_HIP); }
+  }
+  if (hipEventRecord(h->ev1, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { g_last_error = "lifcal_ba_covariance: device failure"; return bail(LIFCAL_BA_ERR_HIP); }
+  float ms = 0.f;
+  (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
+  // ---- outputs ----
+  std::fill(out->camera, out->camera + 17 * 17, 0.0);
+  for (uint32_t i = 0; i < nc; ++i)
+    for (uint32_t k = 0; k < nc; ++k) out->camera[i * 17 + k] = mult * Cp[(size_t)(Q3 + i) * NA + Q3 + k];
+  uint32_t est = 0;
+  for (uint32_t i = 0; i < n; ++i) {
+    if (la[i] < Q3) continue;
+    bool e = true;
+    for (uint32_t k : nulls) if (std::fabs(V[(size_t)i * n + k]) > o.estimable_tol) e = false;
+    if (e) est |= 1u << (la[i] - Q3);
+  }
+  if (out->camera_null) {
+    std::fill(out->camera_null, out->camera_null + 17 * 17, 0.0);
+    for (size_t r2 = 0; r2 < nulls.size() && r2 < 17; ++r2) {
+      double nrm = 0.0;   // the null direction in parameter units (unscaled), unit length over the live arrow slots
+      for (uint32_t i = 0; i < n; ++i) { const double v = V[(size_t)i * n + nulls[r2]] * sc[i]; nrm += v * v; }
+      nrm = nrm > 0.0 ? 1.0 / std::sqrt(nrm) : 0.0;
+      for (uint32_t i = 0; i < n; ++i) if (la[i] >= Q3) out->camera_null[r2 * 17 + (la[i] - Q3)] = V[(size_t)i * n + nulls[r2]] * sc[i] * nrm;
+    }
+  }
+  if (out->pose) {
+    if (want_pose && o.want_pose_blocks && F) { if (hipMemcpy(out->pose, h->cov_G, (size_t)F * 36 * 8, hipMemcpyDeviceToHost) != hipSuccess) { g_last_error = "lifcal_ba_covariance: read-back failed"; return bail(LIFCAL_BA_ERR_HIP); } }
+    else std::fill(out->pose, out->pose + (size_t)F * 36, 0.0);
+  }
+  if (out->pose_band && d.bw) {
+    std::vector<double> zb((size_t)F * d.bw * 36, 0.0);
+    if (want_pose && hipMemcpy(zb.data(), h->cov_Zb, zb.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { g_last_error = "lifcal_ba_covariance: read-back failed"; return bail(LIFCAL_BA_ERR_HIP); }
+    for (uint32_t f = 0; f < F; ++f)   // blocks past the last frame and blocks of frames that are not columns: zero
+      for (uint32_t dd = 1; dd <= d.bw; ++dd) {
+        const bool ok = f + dd < F && d.use_poses && live_saved[f] && live_saved[f + dd] && (int32_t)f != gauge && (int32_t)(f + dd) != gauge;
+        for (uint32_t e = 0; e < 36; ++e) out->pose_band[((size_t)f * d.bw + dd - 1) * 36 + e] = ok ? mult * zb[((size_t)f * d.bw + dd - 1) * 36 + e] : 0.0;
+      }
+  }
+  out->estimable_mask = est; out->null_rank = (uint32_t)nulls.size(); out->gauge_frame_used = gauge; out->live_mask = live_mask;
+  out->sigma2 = sigma2; out->cost = cost; out->seconds = ms * 1e-3;
+  return restore();
+}

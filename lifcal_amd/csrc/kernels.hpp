@@ -25,6 +25,7 @@
 
 #include "../../include/lifcal_ba.h"
 #include "device_model.hpp"
+#include "lm_step.hpp"   // LM_* indices of Dev::lm, LmOpts, the trust-region decisions
 
 namespace lifcal {
 
@@ -32,12 +33,6 @@ constexpr uint32_t DET_NF_MAX = 20;   // widest frame window of a block (Plan::N
 constexpr int SCAL_COST = 0, SCAL_BAD_U = 1, SCAL_GMAX0 = 2, SCAL_N = 2 + 64;
 // host-visible scalars of one LM step
 constexpr int ST_GTD = 0, ST_DDD = 1, ST_STEP2 = 2, ST_X2 = 3, ST_CAND_COST = 4, ST_CHOL_FAIL = 5, ST_GMAX_RED = 6, ST_DIR = 7, ST_N = 8;
-
-// device-resident state of the Levenberg-Marquardt loop (k_lm_control; the host mirrors it once per iteration)
-enum { LM_RADIUS = 0, LM_DECREASE = 1, LM_X_COST = 2, LM_GMAX = 3, LM_ITER = 4, LM_INVALID = 5, LM_STEP_OK = 6, LM_SUCCESSFUL = 7, LM_UNSUCCESSFUL = 8,
-       LM_TERMINATION = 9, LM_COMMIT = 10, LM_FRESH = 11, LM_INITIAL_COST = 12, LM_LAST_REL = 13, LM_LAST_STEP = 14, LM_LAST_CHANGE = 15, LM_SWEEPS = 16,
-       LM_SEQ = 17 /* round counter of the host mirror */, LM_T0 = 18, LM_TICKS_LINEAR = 19 /* 100 MHz ticks: linear solve + candidate evaluation */, LM_N = 24 };
-struct LmOpts { double f_tol, p_tol, g_tol, min_rel_decrease, max_radius, min_radius; int max_iterations; };
 
 // a set of tiles for the value-only kernels (both sweep paths share them)
 struct TileSet { uint32_t n_tiles; const uint32_t *tile_row0, *slot_pt, *slot_fr, *slot_cnt, *ell_lens; const double *ell_u, *ell_v; };
@@ -1214,9 +1209,8 @@ __global__ void k_dir_max(Dev d, unsigned long long* slots) {
 }
 
 // ---------------------------------------------------------------------------------------------
-// Levenberg-Marquardt control on the device (one thread): what lifcal_ba_solve's host loop decides per iteration —
-// ceres 2.1 TrustRegionMinimizer: step validity, the three convergence tests, accept / reject, radius update — from the
-// scalars the sweep and the candidate evaluation left in HBM.  The host enqueues sweep | linear solve | candidate | this |
+// Levenberg-Marquardt control on the device (one thread): the decisions of lm_step.hpp — the ones lifcal_ba_solve's host loop
+// makes per iteration with the same functions — from the scalars the sweep and the candidate evaluation left in HBM.  The host enqueues sweep | linear solve | candidate | this |
 // k_lm_commit | next sweep without waiting and reads the state back once per iteration while the next sweep runs.
 // Unbounded problems on one rank (bounds need the host's line search, ranks need rank-consistent host decisions).
 // ---------------------------------------------------------------------------------------------
@@ -1226,58 +1220,16 @@ LIFCAL_DEV void lm_control_step(const Dev& d, const LmOpts& o, const double* par
   if (lm[LM_TERMINATION] != 0.0) return;
   lm[LM_SWEEPS] += 1.0;
   // the sweep at the head of this iteration: cost / gradient norm of a NEW point, or the same point at a new radius
-  double bad = d.scal[SCAL_BAD_U];
   if (lm[LM_FRESH] != 0.0) {
     double g = 0.0;
     for (int r = 0; r < 64; ++r) g = fmax(g, d.scal[SCAL_GMAX0 + r]);
     g = fmax(g, d.step[ST_GMAX_RED]);
-    lm[LM_X_COST] = d.scal[SCAL_COST]; lm[LM_GMAX] = g;
-    if (lm[LM_INITIAL_COST] < 0.0) {   // the first sweep of the solve
-      lm[LM_INITIAL_COST] = lm[LM_X_COST];
-      if (!(fabs(lm[LM_X_COST]) < 1.7e308)) { lm[LM_TERMINATION] = -1.0; return; }   // non-finite cost at the initial point
-      if (g <= o.g_tol) { lm[LM_TERMINATION] = (double)LIFCAL_BA_TERM_GRADIENT_TOLERANCE; return; }
-    }
-    lm[LM_FRESH] = 0.0;
-  } else {
-    bad = 0.0;   // (the host loop does not re-read the flag of a re-sweep at a smaller radius either)
+    lm_take_sweep(lm, o, d.scal[SCAL_COST], g, d.scal[SCAL_BAD_U]);
+    if (lm[LM_TERMINATION] != 0.0) return;
   }
-  const double x_cost = lm[LM_X_COST];
-  // top of the loop
-  if (lm[LM_ITER] >= (double)o.max_iterations) { lm[LM_TERMINATION] = (double)LIFCAL_BA_TERM_MAX_ITERATIONS; return; }
-  if (lm[LM_STEP_OK] != 0.0 && lm[LM_GMAX] <= o.g_tol) { lm[LM_TERMINATION] = (double)LIFCAL_BA_TERM_GRADIENT_TOLERANCE; return; }
-  if (lm[LM_RADIUS] < o.min_radius) { lm[LM_TERMINATION] = (double)LIFCAL_BA_TERM_MIN_RADIUS; return; }
-  lm[LM_ITER] += 1.0;
-  const double gtd = partial[0], ddd = partial[1], step2 = partial[2], x2 = partial[3];
-  double cand_cost = partial[4];
-  const double chol_fail = d.step[ST_CHOL_FAIL];
-  // model_cost_change = -g^T d - 1/2 d^T J^T J d with (J^T J + Lambda) d = -g  =>  1/2 (d^T Lambda d - g^T d)
-  const double mcc = 0.5 * (ddd - gtd);
-  const bool valid = chol_fail == 0.0 && bad == 0.0 && fabs(mcc) < 1.7e308 && mcc > 0.0;
-  if (!valid) {
-    lm[LM_INVALID] += 1.0;
-    if (lm[LM_INVALID] >= 5.0) { lm[LM_TERMINATION] = (double)LIFCAL_BA_TERM_INVALID_STEPS; return; }
-    lm[LM_RADIUS] *= 0.5; lm[LM_STEP_OK] = 0.0; lm[LM_UNSUCCESSFUL] += 1.0;
-    return;
-  }
-  lm[LM_INVALID] = 0.0;
-  if (!(fabs(cand_cost) < 1.7e308)) cand_cost = 1.7976931348623157e308;
-  const double step_norm = sqrt(step2), x_norm = sqrt(x2);
-  lm[LM_LAST_STEP] = step_norm;
-  if (step_norm <= o.p_tol * (x_norm + o.p_tol)) { lm[LM_TERMINATION] = (double)LIFCAL_BA_TERM_PARAMETER_TOLERANCE; return; }
-  const double cost_change = x_cost - cand_cost;
-  lm[LM_LAST_CHANGE] = cost_change;
-  if (fabs(cost_change) <= o.f_tol * x_cost) { lm[LM_TERMINATION] = (double)LIFCAL_BA_TERM_FUNCTION_TOLERANCE; return; }
-  const double rel = (cand_cost >= 1.7976931348623157e308) ? -1.7976931348623157e308 : cost_change / mcc;
-  lm[LM_LAST_REL] = rel;
-  if (rel > o.min_rel_decrease) {
-    const double t = 2.0 * rel - 1.0;
-    double radius = lm[LM_RADIUS] / fmax(1.0 / 3.0, 1.0 - t * t * t);
-    lm[LM_RADIUS] = fmin(o.max_radius, radius);
-    lm[LM_DECREASE] = 2.0;
-    lm[LM_COMMIT] = 1.0; lm[LM_FRESH] = 1.0; lm[LM_STEP_OK] = 1.0; lm[LM_SUCCESSFUL] += 1.0;
-  } else {
-    lm[LM_RADIUS] = lm[LM_RADIUS] / lm[LM_DECREASE]; lm[LM_DECREASE] *= 2.0; lm[LM_STEP_OK] = 0.0; lm[LM_UNSUCCESSFUL] += 1.0;
-  }
+  if (!lm_open_iteration(lm, o)) return;
+  if (!lm_check_step(lm, partial[0], partial[1], d.step[ST_CHOL_FAIL])) return;
+  lm_judge_step(lm, o, partial[4], partial[2], partial[3]);
 }
 
 // mirror: the state is copied into MAPPED host memory by the kernel itself and the round number is written last (system-scope
@@ -1453,6 +1405,5 @@ __global__ __launch_bounds__(256) void k_stats(Dev d, TileSet ts, const CamConst
 
 }  // namespace lifcal
 #include "bandchol.hpp"   // single-wave LDS-window band Cholesky + back-substitution
-#include "covariance.hpp" // covariance of the parameters: chain without the arrow, selected inversion, multi-RHS back-substitution
 #include "bandchol2.hpp"  // the same as segment chains: twisted (two-ended) factorisation on two workgroups
 #include "bandchol3.hpp"  // block odd-even reduction over many workgroups (long sequences)

@@ -4,9 +4,8 @@
 // residual-block construction loop, lifcal_ba_solve() replaces ceres::Solve() with a Levenberg–Marquardt
 // trust-region loop whose arithmetic stays in HBM (only a handful of scalars per iteration cross PCIe
 // for the accept/reject decision), lifcal_ba_reproj_stats() replaces calcReprojectionError() (:1026-1103).
-// Trust-region logic follows Ceres 2.1 TrustRegionMinimizer / LevenbergMarquardtStrategy (out-of-tree,
-// restated): radius 1e4, accept if rho > 1e-3, radius /= max(1/3, 1-(2 rho-1)^3), reject: radius /= 2^k,
-// Jacobi scaling fixed at iteration 0, LM diagonal clamp [1e-6, 1e32].
+// Trust-region logic follows Ceres 2.1 TrustRegionMinimizer / LevenbergMarquardtStrategy (out-of-tree, restated in
+// lm_step.hpp, the one place where the rules are written); Jacobi scaling fixed at iteration 0, LM diagonal clamp [1e-6, 1e32].
 #include <hip/hip_runtime.h>
 #include <hip/hip_ext.h>
 
@@ -251,6 +250,28 @@ int launch_tables(lifcal_ba_handle* h, const double* cam, const double* views, C
   return 0;
 }
 
+// distance constraints at `pts`: cost and blocks, or (cost_only) the cost alone, added to *out.  Deterministic: one thread sums
+void launch_constraints(lifcal_ba_handle* h, int cost_only, const double* pts, double* out) {
+  const Dev& d = h->d;
+  if (d.M_local) hipLaunchKernelGGL(k_constraints, dim3(d.deterministic ? 1 : (d.M_local + 63) / 64), dim3(d.deterministic ? 1 : 64), 0, h->stream, d, cost_only, pts, out);
+}
+
+// cost of a parameter set (its tables, its points) through the value-only kernel, both tile sets, + the constraint term, added to *out
+int launch_value_cost(lifcal_ba_handle* h, const CamConsts* camc, const double* ft, const double* lt, const double* pts, double* out) {
+  const Dev& d = h->d;
+  for (const TileSet* ts : {&h->ts1, &h->ts2}) {
+    if (!ts->n_tiles) continue;
+    const uint32_t grid = std::max(1u, std::min((ts->n_tiles + 3) / 4, 1024u));
+#define CALL_COST(NR, TAN, ADJ) hipLaunchKernelGGL((k_cost<NR, TAN, ADJ>), dim3(grid), dim3(256), 0, h->stream, d, *ts, camc, ft, lt, pts, out)
+    DISPATCH_CFG(h, CALL_COST);
+#undef CALL_COST
+    if (d.deterministic) hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(64), 0, h->stream, (const double*)d.det_slots, grid, 1u, out);
+  }
+  launch_constraints(h, 1, pts, out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // the kernels that turn observations into blocks.  mode 1 = Hessian diagonal only (Jacobi scaling, iteration 0)
 int launch_blocks(lifcal_ba_handle* h, double radius, int mode, bool zeroed) {
   Dev& d = h->d;
@@ -300,7 +321,7 @@ int launch_blocks(lifcal_ba_handle* h, double radius, int mode, bool zeroed) {
 #undef CALL_SWEEP
   }
   if (prof && !d.n_blocks) HIP_TRY(hipEventRecord(ev_b, h->stream));
-  if (d.M_local) hipLaunchKernelGGL(k_constraints, dim3(d.deterministic ? 1 : (d.M_local + 63) / 64), dim3(d.deterministic ? 1 : 64), 0, h->stream, d, 0, (const double*)d.pts, d.scal + SCAL_COST);
+  launch_constraints(h, 0, d.pts, d.scal + SCAL_COST);
   if (d.Q && d.use_points) hipLaunchKernelGGL(k_promote_diag, dim3((d.Q + 63) / 64), dim3(64), 0, h->stream, d);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -402,19 +423,8 @@ int launch_candidate(lifcal_ba_handle* h) {
   }
   HIP_TRY(hipGetLastError());
   if (int rc = launch_tables(h, d.cam_c, d.views_c, d.camc_c, d.ft_c, d.lt_c, false, true)) return rc;
-  const double* pts_eval = d.use_points ? d.pts_c : d.pts;
-  for (const TileSet* ts : {&h->ts1, &h->ts2}) {
-    if (!ts->n_tiles) continue;
-    const uint32_t grid = std::max(1u, std::min((ts->n_tiles + 3) / 4, 1024u));
-#define CALL_COST(NR, TAN, ADJ) hipLaunchKernelGGL((k_cost<NR, TAN, ADJ>), dim3(grid), dim3(256), 0, h->stream, d, *ts, (const CamConsts*)d.camc_c, (const double*)d.ft_c, (const double*)d.lt_c, pts_eval, h->partial + 4)
-    DISPATCH_CFG(h, CALL_COST);
-#undef CALL_COST
-    if (d.deterministic) hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(64), 0, h->stream, (const double*)d.det_slots, grid, 1u, h->partial + 4);
-  }
-  if (d.M_local) hipLaunchKernelGGL(k_constraints, dim3(d.deterministic ? 1 : (d.M_local + 63) / 64), dim3(d.deterministic ? 1 : 64), 0, h->stream, d, 1, pts_eval, h->partial + 4);
-  HIP_TRY(hipGetLastError());
-  if (int rc = do_allreduce(h, h->partial, 8)) return rc;
-  return 0;
+  if (int rc = launch_value_cost(h, d.camc_c, d.ft_c, d.lt_c, d.use_points ? d.pts_c : d.pts, h->partial + 4)) return rc;
+  return do_allreduce(h, h->partial, 8);
 }
 
 // fp64 cost of the CURRENT point through the value-only kernel (options.precision = 1: the LM decisions compare costs of one
@@ -422,23 +432,17 @@ int launch_candidate(lifcal_ba_handle* h) {
 int cost64_current(lifcal_ba_handle* h, double* cost) {
   Dev& d = h->d;
   HIP_TRY(hipMemsetAsync(h->partial, 0, 8 * sizeof(double), h->stream));
-  const double* pts_eval = d.pts;
-  for (const TileSet* ts : {&h->ts1, &h->ts2}) {
-    if (!ts->n_tiles) continue;
-    const uint32_t grid = std::max(1u, std::min((ts->n_tiles + 3) / 4, 1024u));
-#define CALL_COST0(NR, TAN, ADJ) hipLaunchKernelGGL((k_cost<NR, TAN, ADJ>), dim3(grid), dim3(256), 0, h->stream, d, *ts, (const CamConsts*)d.camc, (const double*)d.ft, (const double*)d.lt, pts_eval, h->partial + 4)
-    DISPATCH_CFG(h, CALL_COST0);
-#undef CALL_COST0
-    if (d.deterministic) hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(64), 0, h->stream, (const double*)d.det_slots, grid, 1u, h->partial + 4);
-  }
-  if (d.M_local) hipLaunchKernelGGL(k_constraints, dim3(d.deterministic ? 1 : (d.M_local + 63) / 64), dim3(d.deterministic ? 1 : 64), 0, h->stream, d, 1, pts_eval, h->partial + 4);
-  HIP_TRY(hipGetLastError());
+  if (int rc = launch_value_cost(h, d.camc, d.ft, d.lt, d.pts, h->partial + 4)) return rc;
   if (int rc = do_allreduce(h, h->partial, 8)) return rc;
-  double hp[8];
-  HIP_TRY(hipMemcpyAsync(hp, h->partial, sizeof(hp), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(cost, h->partial + 4, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
-  *cost = hp[4];
   return 0;
+}
+
+void swap_current_candidate(lifcal_ba_handle* h) {
+  Dev& d = h->d;
+  std::swap(d.cam, d.cam_c); std::swap(d.views, d.views_c);
+  if (d.use_points) std::swap(d.pts, d.pts_c);
 }
 
 // ---- Armijo line search (bounded problems) ---------------------------------------------------------------------
@@ -458,8 +462,7 @@ int launch_apply_step(lifcal_ba_handle* h, double t) {
 int eval_trial(lifcal_ba_handle* h, double t, double radius, LsSample* smp) {
   Dev& d = h->d;
   if (int rc = launch_apply_step(h, t)) return rc;
-  auto swap_all = [&]() { std::swap(d.cam, d.cam_c); std::swap(d.views, d.views_c); if (d.use_points) std::swap(d.pts, d.pts_c); };
-  swap_all();
+  swap_current_candidate(h);
   int rc = launch_tables(h, d.cam, d.views, d.camc, d.ft, d.lt, true, true, h->red_block, h->red_count, d.step, ST_N, d.ltf);
   if (!rc) rc = launch_blocks(h, radius, 0, true);
   if (!rc && d.use_points && d.n_special) { hipLaunchKernelGGL(k_schur, dim3((d.n_special + 3) / 4), dim3(256), 0, h->stream, d, radius); }
@@ -474,20 +477,8 @@ int eval_trial(lifcal_ba_handle* h, double t, double radius, LsSample* smp) {
   // loop come from the fp64 value kernel — near convergence the offset between the two arithmetics (~1e-7 relative) is far larger
   // than the Armijo margin, so the trial value is taken from the SAME fp64 kernel on the trial point's tables (ls_buf[3])
   const bool value64 = h->opt.precision == 1;
-  if (!rc && value64) {
-    const double* pts_eval = d.pts;   // (swapped: the trial point)
-    for (const TileSet* ts : {&h->ts1, &h->ts2}) {
-      if (!ts->n_tiles) continue;
-      const uint32_t grid = std::max(1u, std::min((ts->n_tiles + 3) / 4, 1024u));
-#define CALL_COSTT(NR, TAN, ADJ) hipLaunchKernelGGL((k_cost<NR, TAN, ADJ>), dim3(grid), dim3(256), 0, h->stream, d, *ts, (const CamConsts*)d.camc, (const double*)d.ft, (const double*)d.lt, pts_eval, h->ls_buf + 3)
-      DISPATCH_CFG(h, CALL_COSTT);
-#undef CALL_COSTT
-      if (d.deterministic) hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(64), 0, h->stream, (const double*)d.det_slots, grid, 1u, h->ls_buf + 3);
-    }
-    if (d.M_local) hipLaunchKernelGGL(k_constraints, dim3(d.deterministic ? 1 : (d.M_local + 63) / 64), dim3(d.deterministic ? 1 : 64), 0, h->stream, d, 1, pts_eval, h->ls_buf + 3);
-    if (hipGetLastError() != hipSuccess) rc = LIFCAL_BA_ERR_HIP;
-  }
-  swap_all();
+  if (!rc && value64) rc = launch_value_cost(h, d.camc, d.ft, d.lt, d.pts, h->ls_buf + 3);   // (swapped: the trial point)
+  swap_current_candidate(h);
   if (rc) return rc;
   if (int rc2 = do_allreduce(h, h->ls_buf, value64 ? 4 : 3)) return rc2;
   double hb[8], cost;
@@ -505,18 +496,71 @@ struct StepScalars { double gtd, ddd, step2, x2, cand_cost, chol_fail; };
 int read_step_scalars(lifcal_ba_handle* h, StepScalars* s) {
   HIP_TRY(hipMemcpyAsync(h->h_scal, h->d.step, (ST_N + 8) * sizeof(double), hipMemcpyDeviceToHost, h->stream));   // step | partial: contiguous
   HIP_TRY(hipStreamSynchronize(h->stream));
-  const double* a = h->h_scal; const double* p = h->h_scal + ST_N;
   // p[0..3]: all-reduced sums over every rank's points + the replicated camera / pose part contributed by rank 0 alone
   // (k_update_reduced): identical bits on every rank, as the branches they steer require
-  s->gtd = p[0]; s->ddd = p[1]; s->step2 = p[2]; s->x2 = p[3];
-  s->cand_cost = p[4]; s->chol_fail = a[ST_CHOL_FAIL];
+  const double* p = h->h_scal + ST_N;
+  *s = {p[0], p[1], p[2], p[3], p[4], h->h_scal[ST_CHOL_FAIL]};
   return 0;
 }
 
-void swap_current_candidate(lifcal_ba_handle* h) {
+// max |delta| over ALL columns for the minimum-step test of the line search (ceres LineSearch::min_step_size / max_abs(direction)):
+// the camera + pose part is replicated, the point part is spread over the ranks -> per-rank slots, all-reduced.
+// (A rank-local maximum here once let one rank leave the search while the other entered the next trial's all-reduce.)
+int step_dir_max(lifcal_ba_handle* h, double* dir_max) {
   Dev& d = h->d;
-  std::swap(d.cam, d.cam_c); std::swap(d.views, d.views_c);
-  if (d.use_points) std::swap(d.pts, d.pts_c);
+  HIP_TRY(hipMemsetAsync(h->dirmax_buf, 0, 65 * sizeof(double), h->stream));
+  const uint32_t n = std::max(std::max(d.n_red, d.n_owned), 1u);
+  hipLaunchKernelGGL(k_dir_max, dim3((n + 255) / 256), dim3(256), 0, h->stream, d, (unsigned long long*)h->dirmax_buf);
+  HIP_TRY(hipGetLastError());
+  if (int rc = do_allreduce(h, h->dirmax_buf, 65)) return rc;
+  double hm[65];
+  HIP_TRY(hipMemcpyAsync(hm, h->dirmax_buf, sizeof(hm), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  *dir_max = hm[64];
+  for (int r = 0; r < h->opt.world_size; ++r) *dir_max = std::max(*dir_max, hm[r]);
+  return 0;
+}
+
+// ceres TrustRegionMinimizer::DoLineSearch: Armijo along the projected step, CUBIC interpolation, at most 20 trials;
+// phi(1) is the candidate cost already evaluated (*cand_cost on entry), the gradient at a trial point is only needed when the
+// test fails.  A search that ran replaces *cand_cost, *step2 and *x2 by those of the candidate at the chosen step length (the
+// model cost change stays that of the full step); its trial sweeps overwrite the blocks of the current point.
+int line_search(lifcal_ba_handle* h, double x_cost, double g0, double radius, int iteration, double* cand_cost, double* step2, double* x2) {
+  Dev& d = h->d;
+  const double suff = 1e-4;
+  if (std::isfinite(*cand_cost) && *cand_cost <= x_cost + suff * g0 * 1.0) return 0;
+  LsSample init, prev, cur;
+  init.x = 0; init.value = x_cost; init.gradient = g0; init.value_valid = init.gradient_valid = true;
+  if (int rc = eval_trial(h, 1.0, radius, &cur)) return rc;
+  double dir_max = 0;
+  if (int rc = step_dir_max(h, &dir_max)) return rc;
+  int ls_iter = 0; bool ls_ok = true;
+  if (h->trace) fprintf(stderr, "[lifcal_ba r%d] it %d line search: dir_max %.17g phi(1) %.17g phi'(1) %.17g\n", h->opt.rank, iteration, dir_max, cur.value, cur.gradient);
+  while (!cur.value_valid || cur.value > x_cost + suff * g0 * cur.x) {
+    if (++ls_iter >= 20) { ls_ok = false; break; }
+    const double lo_b = 1e-3 * cur.x, hi_b = 0.6 * cur.x;
+    double tnew;
+    if (!cur.value_valid) tnew = std::min(std::max(cur.x * 0.5, lo_b), hi_b);
+    else { std::vector<LsSample> smp{init, cur}; if (prev.value_valid) smp.push_back(prev); tnew = ls_minimize(smp, lo_b, hi_b); }
+    if (tnew * dir_max < 1e-9) { ls_ok = false; break; }
+    prev = cur;
+    if (int rc = eval_trial(h, tnew, radius, &cur)) return rc;
+    if (h->trace) fprintf(stderr, "[lifcal_ba r%d] it %d line search trial %d: t %.17g phi %.17g phi' %.17g\n", h->opt.rank, iteration, ls_iter, tnew, cur.value, cur.gradient);
+  }
+  const double t_opt = ls_ok ? cur.x : 1.0;
+  if (int rc = launch_apply_step(h, t_opt)) return rc;
+  HIP_TRY(hipMemsetAsync(h->partial, 0, 8 * sizeof(double), h->stream));
+  if (int rc = launch_tables(h, d.cam_c, d.views_c, d.camc_c, d.ft_c, d.lt_c, false, true)) return rc;
+  if (int rc = launch_value_cost(h, d.camc_c, d.ft_c, d.lt_c, d.use_points ? d.pts_c : d.pts, h->partial + 4)) return rc;
+  if (int rc = do_allreduce(h, h->partial, 8)) return rc;
+  if (int rc = do_allreduce(h, h->ls_buf, 2)) return rc;
+  double hb[8], hp[8];
+  HIP_TRY(hipMemcpyAsync(hb, h->ls_buf, sizeof(hb), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipMemcpyAsync(hp, h->partial, sizeof(hp), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  *cand_cost = hp[4]; *step2 = hb[0]; *x2 = hb[1];
+  if (getenv("LIFCAL_DEBUG_LS")) fprintf(stderr, "[lifcal_ba] line search: %d backtracks, t = %.6g\n", ls_iter, t_opt);
+  return 0;
 }
 
 int upload_parameters(lifcal_ba_handle* h) {
@@ -563,43 +607,6 @@ int download_parameters(lifcal_ba_handle* h) {
   }
   HIP_TRY(hipStreamSynchronize(h->stream));
   return 0;
-}
-
-// symmetric eigen-decomposition of a small n x n matrix (cyclic Jacobi, fixed sweep order: deterministic): A row-major, destroyed;
-// w[i] eigenvalues, V[r * n + i] the unit eigenvector of w[i] in column i
-void sym_eig_jacobi(uint32_t n, std::vector<double>& A, std::vector<double>& w, std::vector<double>& V) {
-  V.assign((size_t)n * n, 0.0);
-  for (uint32_t i = 0; i < n; ++i) V[(size_t)i * n + i] = 1.0;
-  for (int sweep = 0; sweep < 100; ++sweep) {
-    double off = 0.0, tot = 0.0;
-    for (uint32_t p = 0; p < n; ++p)
-      for (uint32_t q = 0; q < n; ++q) { const double v = A[(size_t)p * n + q] * A[(size_t)p * n + q]; tot += v; if (p != q) off += v; }
-    if (off <= 1e-34 * tot || off == 0.0) break;
-    for (uint32_t p = 0; p + 1 < n; ++p)
-      for (uint32_t q = p + 1; q < n; ++q) {
-        const double apq = A[(size_t)p * n + q];
-        if (apq == 0.0) continue;
-        const double app = A[(size_t)p * n + p], aqq = A[(size_t)q * n + q];
-        const double theta = (aqq - app) / (2.0 * apq);
-        const double t = (theta >= 0.0 ? 1.0 : -1.0) / (std::fabs(theta) + std::sqrt(theta * theta + 1.0));
-        const double c = 1.0 / std::sqrt(t * t + 1.0), sn = t * c;
-        for (uint32_t k = 0; k < n; ++k) {   // A <- A J (columns p, q)
-          const double akp = A[(size_t)k * n + p], akq = A[(size_t)k * n + q];
-          A[(size_t)k * n + p] = c * akp - sn * akq; A[(size_t)k * n + q] = sn * akp + c * akq;
-        }
-        for (uint32_t k = 0; k < n; ++k) {   // A <- J^T A (rows p, q)
-          const double apk = A[(size_t)p * n + k], aqk = A[(size_t)q * n + k];
-          A[(size_t)p * n + k] = c * apk - sn * aqk; A[(size_t)q * n + k] = sn * apk + c * aqk;
-        }
-        A[(size_t)p * n + q] = 0.0; A[(size_t)q * n + p] = 0.0;
-        for (uint32_t k = 0; k < n; ++k) {
-          const double vkp = V[(size_t)k * n + p], vkq = V[(size_t)k * n + q];
-          V[(size_t)k * n + p] = c * vkp - sn * vkq; V[(size_t)k * n + q] = sn * vkp + c * vkq;
-        }
-      }
-  }
-  w.resize(n);
-  for (uint32_t i = 0; i < n; ++i) w[i] = A[(size_t)i * n + i];
 }
 
 }  // namespace
@@ -999,7 +1006,6 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
     if (h->bandw_ok) {
       A(h->Lpanel, (size_t)std::max(1u, d.F) * (6 * (size_t)d.bw + d.NA + 1) * 6);
       if (hipFuncSetAttribute((const void*)k_band_chol_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bandw_lds) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP);
-      if (hipFuncSetAttribute((const void*)k_cov_chol_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->bandw_lds) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP);
       if (hipFuncSetAttribute((const void*)k_band_backsolve_w, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->backw_lds) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP);
       // long enough for two chains to pay: eliminate from both ends (LIFCAL_TWISTED=0: the single chain)
       h->twisted = d.use_poses && d.bw >= 1 && d.F >= 3 * d.bw + 8 && !(getenv("LIFCAL_TWISTED") && atoi(getenv("LIFCAL_TWISTED")) == 0);
@@ -1233,15 +1239,11 @@ int lifcal_ba_sweep(lifcal_ba_handle* h, double radius, lifcal_ba_sweep_out* out
 // host-induced idle time), and no copy kernel or event record sits between the kernels of an iteration (each a barrier packet:
 // ~5 us of idle queue; the split of the loop's time comes from s_memrealtime stamps taken by the kernels themselves).  The sweep
 // enqueued behind the terminating decision is the only wasted work.  Unbounded problems on one rank.
-static int solve_device_loop(lifcal_ba_handle* h, lifcal_ba_summary* s, double t_start) {
+static int solve_device_loop(lifcal_ba_handle* h, const LmOpts& lo, lifcal_ba_summary* s, double t_start) {
   Dev& d = h->d;
   const lifcal_ba_options& o = h->opt;
-  double lm0[LM_N];
-  for (int i = 0; i < LM_N; ++i) lm0[i] = 0.0;
-  lm0[LM_RADIUS] = o.initial_radius; lm0[LM_DECREASE] = 2.0; lm0[LM_STEP_OK] = 1.0; lm0[LM_FRESH] = 1.0; lm0[LM_INITIAL_COST] = -1.0;
-  std::memcpy(h->h_lm + LM_N, lm0, sizeof(lm0));   // (staging half of the mapped buffer: no synchronisation before the loop starts)
-  HIP_TRY(hipMemcpyAsync(d.lm, h->h_lm + LM_N, sizeof(lm0), hipMemcpyHostToDevice, h->stream));
-  const LmOpts lo{o.function_tolerance, o.parameter_tolerance, o.gradient_tolerance, o.min_relative_decrease, o.max_radius, o.min_radius, o.max_iterations};
+  lm_reset(h->h_lm + LM_N, o.initial_radius);   // (staging half of the mapped buffer: no synchronisation before the loop starts)
+  HIP_TRY(hipMemcpyAsync(d.lm, h->h_lm + LM_N, LM_N * sizeof(double), hipMemcpyHostToDevice, h->stream));
   double t0 = now_s();
   if (int rc = launch_sweep(h, -1.0)) return rc;
   const uint32_t commit_grid = std::max(1u, std::min(1024u, (3 * d.P + 6 * d.F + 255) / 256));
@@ -1273,9 +1275,7 @@ static int solve_device_loop(lifcal_ba_handle* h, lifcal_ba_summary* s, double t
   HIP_TRY(hipStreamSynchronize(h->stream));
   const double* lm = h->h_lm;
   if (lm[LM_TERMINATION] < 0.0) { g_last_error = "non-finite cost at the initial point"; return LIFCAL_BA_ERR_NUMERIC; }
-  s->initial_cost = lm[LM_INITIAL_COST]; s->final_cost = lm[LM_X_COST]; s->final_radius = lm[LM_RADIUS]; s->final_gradient_max_norm = lm[LM_GMAX];
-  s->iterations = (int32_t)lm[LM_ITER]; s->successful_steps = (int32_t)lm[LM_SUCCESSFUL]; s->unsuccessful_steps = (int32_t)lm[LM_UNSUCCESSFUL];
-  s->termination = lm[LM_TERMINATION] != 0.0 ? (int32_t)lm[LM_TERMINATION] : LIFCAL_BA_TERM_MAX_ITERATIONS;
+  lm_fill_summary(lm, s);
   if (int rc = download_parameters(h)) return rc;
   s->seconds_total = now_s() - t_start;
   s->seconds_linear_solve = 1e-8 * lm[LM_TICKS_LINEAR];                    // linear solve + candidate evaluation: 100 MHz ticks from k_finalize's start to k_lm_control's
@@ -1290,313 +1290,57 @@ int lifcal_ba_solve(lifcal_ba_handle* h, lifcal_ba_summary* s) {
   const double t_start = now_s();
   std::memset(s, 0, sizeof(*s));
   if (int rc = upload_parameters(h)) return rc;
+  const LmOpts lo{o.function_tolerance, o.parameter_tolerance, o.gradient_tolerance, o.min_relative_decrease, o.max_radius, o.min_radius, o.max_iterations};
   // decisions on the device where the host has none of its own to make (LIFCAL_HOST_LM=1: the host loop below, e.g. for LIFCAL_TRACE)
   if (!h->constrained && o.world_size == 1 && o.precision == 0 && !h->trace && !o.verbose && getenv("LIFCAL_HOST_LM") == nullptr)
-    return solve_device_loop(h, s, t_start);
-  double radius = o.initial_radius, decrease_factor = 2.0;
-  double x_cost, gmax, bad;
+    return solve_device_loop(h, lo, s, t_start);
+  // the host loop: launches, read-backs and printing here, every decision in lm_step.hpp (the functions k_lm_control calls)
+  double lm[LM_N];
+  lm_reset(lm, o.initial_radius);
+  double cost, gmax, bad;
   double t0 = now_s();
-  if (int rc = launch_sweep(h, radius)) return rc;
-  if (int rc = read_sweep_scalars(h, &x_cost, &gmax, &bad)) return rc;
-  if (o.precision == 1) { if (int rc = cost64_current(h, &x_cost)) return rc; }
+  if (int rc = launch_sweep(h, lm[LM_RADIUS])) return rc;
+  if (int rc = read_sweep_scalars(h, &cost, &gmax, &bad)) return rc;
+  if (o.precision == 1) { if (int rc = cost64_current(h, &cost)) return rc; }
   s->seconds_sweep += now_s() - t0;
-  if (!std::isfinite(x_cost)) { g_last_error = "non-finite cost at the initial point"; return LIFCAL_BA_ERR_NUMERIC; }
-  s->initial_cost = x_cost;
-  int iteration = 0, invalid_steps = 0;
-  bool step_successful = true, system_ready = true;
-  if (o.verbose) printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n%4d % .6e    0.00e+00 %10.2e   0.00e+00   0.00e+00 %9.2e\n", 0, x_cost, gmax, radius);
-  s->termination = LIFCAL_BA_TERM_NONE;
-  if (gmax <= o.gradient_tolerance) s->termination = LIFCAL_BA_TERM_GRADIENT_TOLERANCE;
-  while (s->termination == LIFCAL_BA_TERM_NONE) {
-    if (iteration >= o.max_iterations) { s->termination = LIFCAL_BA_TERM_MAX_ITERATIONS; break; }
-    if (step_successful && gmax <= o.gradient_tolerance) { s->termination = LIFCAL_BA_TERM_GRADIENT_TOLERANCE; break; }
-    if (radius < o.min_radius) { s->termination = LIFCAL_BA_TERM_MIN_RADIUS; break; }
-    ++iteration;
-    if (!system_ready) {  // same point, new radius: the fused sweep is cheap enough to simply run again
+  lm_take_sweep(lm, lo, cost, gmax, bad);
+  if (lm[LM_TERMINATION] < 0.0) { g_last_error = "non-finite cost at the initial point"; return LIFCAL_BA_ERR_NUMERIC; }
+  if (o.verbose) printf("iter      cost      cost_change  |gradient|   |step|    tr_ratio  tr_radius\n%4d % .6e    0.00e+00 %10.2e   0.00e+00   0.00e+00 %9.2e\n", 0, lm[LM_X_COST], lm[LM_GMAX], lm[LM_RADIUS]);
+  while (lm[LM_TERMINATION] == 0.0 && lm_open_iteration(lm, lo)) {
+    const int iteration = (int)lm[LM_ITER];
+    const double radius = lm[LM_RADIUS], x_cost = lm[LM_X_COST];
+    if (lm[LM_STEP_OK] == 0.0) {  // same point, new radius: the fused sweep is cheap enough to simply run again
       t0 = now_s();
       if (int rc = launch_sweep(h, radius)) return rc;
       s->seconds_sweep += now_s() - t0;
     }
-    system_ready = false;
     t0 = now_s();
     if (int rc = launch_linear_solve(h)) return rc;
     if (int rc = launch_candidate(h)) return rc;
     StepScalars st;
     if (int rc = read_step_scalars(h, &st)) return rc;
     s->seconds_linear_solve += now_s() - t0;
-    // model_cost_change = -g^T d - 1/2 d^T J^T J d with (J^T J + Lambda) d = -g  =>  1/2 (d^T Lambda d - g^T d)
-    const double model_cost_change = 0.5 * (st.ddd - st.gtd);
-    if (h->trace) fprintf(stderr, "[lifcal_ba r%d] it %d radius %.17g x_cost %.17g cand %.17g gtd %.17g ddd %.17g step2 %.17g chol_fail %g bad %g\n", o.rank, iteration, radius, x_cost, st.cand_cost, st.gtd, st.ddd, st.step2, st.chol_fail, bad);
-    const bool valid = st.chol_fail == 0.0 && bad == 0.0 && std::isfinite(model_cost_change) && model_cost_change > 0.0;
-    if (!valid) {
-      if (++invalid_steps >= 5) { s->termination = LIFCAL_BA_TERM_INVALID_STEPS; break; }
-      radius *= 0.5; step_successful = false; ++s->unsuccessful_steps;
-      bad = 0.0;
-      continue;
-    }
-    invalid_steps = 0;
-    double cand_cost = st.cand_cost;
-    if (!std::isfinite(cand_cost)) cand_cost = std::numeric_limits<double>::max();
-    double step2 = st.step2, x2 = st.x2;
-    if (h->constrained) {
-      // ceres TrustRegionMinimizer::DoLineSearch: Armijo along the projected step, CUBIC interpolation, at most 20 trials;
-      // phi(1) is the candidate cost already evaluated, the gradient at a trial point is only needed when the test fails
-      const double g0 = st.gtd;
-      const double suff = 1e-4;
-      bool armijo_ok = std::isfinite(st.cand_cost) && st.cand_cost <= x_cost + suff * g0 * 1.0;
-      if (!armijo_ok) {
-        LsSample init, prev, cur;
-        init.x = 0; init.value = x_cost; init.gradient = g0; init.value_valid = init.gradient_valid = true;
-        if (int rc = eval_trial(h, 1.0, radius, &cur)) return rc;
-        // max |delta| over ALL columns for the minimum-step test (ceres LineSearch::min_step_size / max_abs(direction)):
-        // the camera + pose part is replicated, the point part is spread over the ranks -> per-rank slots, all-reduced.
-        // (A rank-local maximum here once let one rank leave the search while the other entered the next trial's all-reduce.)
-        double dir_max = 0;
-        {
-          Dev& d = h->d;
-          HIP_TRY(hipMemsetAsync(h->dirmax_buf, 0, 65 * sizeof(double), h->stream));
-          const uint32_t n = std::max(std::max(d.n_red, d.n_owned), 1u);
-          hipLaunchKernelGGL(k_dir_max, dim3((n + 255) / 256), dim3(256), 0, h->stream, d, (unsigned long long*)h->dirmax_buf);
-          HIP_TRY(hipGetLastError());
-          if (int rc = do_allreduce(h, h->dirmax_buf, 65)) return rc;
-          double hm[65];
-          HIP_TRY(hipMemcpyAsync(hm, h->dirmax_buf, sizeof(hm), hipMemcpyDeviceToHost, h->stream));
-          HIP_TRY(hipStreamSynchronize(h->stream));
-          for (int r = 0; r < o.world_size; ++r) dir_max = std::max(dir_max, hm[r]);
-          dir_max = std::max(dir_max, hm[64]);
-        }
-        int ls_iter = 0; bool ls_ok = true;
-        if (h->trace) fprintf(stderr, "[lifcal_ba r%d] it %d line search: dir_max %.17g phi(1) %.17g phi'(1) %.17g\n", o.rank, iteration, dir_max, cur.value, cur.gradient);
-        while (!cur.value_valid || cur.value > x_cost + suff * g0 * cur.x) {
-          if (++ls_iter >= 20) { ls_ok = false; break; }
-          const double lo_b = 1e-3 * cur.x, hi_b = 0.6 * cur.x;
-          double tnew;
-          if (!cur.value_valid) tnew = std::min(std::max(cur.x * 0.5, lo_b), hi_b);
-          else { std::vector<LsSample> smp{init, cur}; if (prev.value_valid) smp.push_back(prev); tnew = ls_minimize(smp, lo_b, hi_b); }
-          if (tnew * dir_max < 1e-9) { ls_ok = false; break; }
-          prev = cur;
-          if (int rc = eval_trial(h, tnew, radius, &cur)) return rc;
-          if (h->trace) fprintf(stderr, "[lifcal_ba r%d] it %d line search trial %d: t %.17g phi %.17g phi' %.17g\n", o.rank, iteration, ls_iter, tnew, cur.value, cur.gradient);
-        }
-        const double t_opt = ls_ok ? cur.x : 1.0;
-        // candidate at the chosen step length, its cost and the step norm (the model cost change stays that of the full step)
-        if (int rc = launch_apply_step(h, t_opt)) return rc;
-        HIP_TRY(hipMemsetAsync(h->partial, 0, 8 * sizeof(double), h->stream));
-        if (int rc = launch_tables(h, h->d.cam_c, h->d.views_c, h->d.camc_c, h->d.ft_c, h->d.lt_c, false, true)) return rc;
-        {
-          Dev& d = h->d;
-          const double* pts_eval = d.use_points ? d.pts_c : d.pts;
-          for (const TileSet* ts : {&h->ts1, &h->ts2}) {
-            if (!ts->n_tiles) continue;
-            const uint32_t grid = std::max(1u, std::min((ts->n_tiles + 3) / 4, 1024u));
-#define CALL_COST2(NR, TAN, ADJ) hipLaunchKernelGGL((k_cost<NR, TAN, ADJ>), dim3(grid), dim3(256), 0, h->stream, d, *ts, (const CamConsts*)d.camc_c, (const double*)d.ft_c, (const double*)d.lt_c, pts_eval, h->partial + 4)
-            DISPATCH_CFG(h, CALL_COST2);
-#undef CALL_COST2
-            if (d.deterministic) hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(64), 0, h->stream, (const double*)d.det_slots, grid, 1u, h->partial + 4);
-          }
-          if (d.M_local) hipLaunchKernelGGL(k_constraints, dim3(d.deterministic ? 1 : (d.M_local + 63) / 64), dim3(d.deterministic ? 1 : 64), 0, h->stream, d, 1, pts_eval, h->partial + 4);
-          HIP_TRY(hipGetLastError());
-          if (int rc = do_allreduce(h, h->partial, 8)) return rc;
-          if (int rc = do_allreduce(h, h->ls_buf, 2)) return rc;
-          double hb[8], hp[8];
-          HIP_TRY(hipMemcpyAsync(hb, h->ls_buf, sizeof(hb), hipMemcpyDeviceToHost, h->stream));
-          HIP_TRY(hipMemcpyAsync(hp, h->partial, sizeof(hp), hipMemcpyDeviceToHost, h->stream));
-          HIP_TRY(hipStreamSynchronize(h->stream));
-          cand_cost = std::isfinite(hp[4]) ? hp[4] : std::numeric_limits<double>::max();
-          step2 = hb[0]; x2 = hb[1];
-        }
-        system_ready = false;   // the trial sweeps overwrote the blocks of the current point
-        if (getenv("LIFCAL_DEBUG_LS")) fprintf(stderr, "[lifcal_ba] line search: %d backtracks, t = %.6g\n", ls_iter, t_opt);
-      }
-    }
-    const double step_norm = std::sqrt(step2), x_norm = std::sqrt(x2);
-    if (step_norm <= o.parameter_tolerance * (x_norm + o.parameter_tolerance)) { s->termination = LIFCAL_BA_TERM_PARAMETER_TOLERANCE; break; }
-    const double cost_change = x_cost - cand_cost;
-    if (std::fabs(cost_change) <= o.function_tolerance * x_cost) { s->termination = LIFCAL_BA_TERM_FUNCTION_TOLERANCE; break; }
-    const double rel = (cand_cost >= std::numeric_limits<double>::max()) ? std::numeric_limits<double>::lowest() : cost_change / model_cost_change;
-    if (rel > o.min_relative_decrease) {
+    if (h->trace) fprintf(stderr, "[lifcal_ba r%d] it %d radius %.17g x_cost %.17g cand %.17g gtd %.17g ddd %.17g step2 %.17g chol_fail %g bad %g\n", o.rank, iteration, radius, x_cost, st.cand_cost, st.gtd, st.ddd, st.step2, st.chol_fail, lm[LM_BAD]);
+    if (!lm_check_step(lm, st.gtd, st.ddd, st.chol_fail)) continue;
+    double cand_cost = st.cand_cost, step2 = st.step2, x2 = st.x2;
+    if (h->constrained) { if (int rc = line_search(h, x_cost, st.gtd, radius, iteration, &cand_cost, &step2, &x2)) return rc; }
+    lm_judge_step(lm, lo, cand_cost, step2, x2);
+    if (lm[LM_TERMINATION] != 0.0) break;
+    if (lm[LM_COMMIT] != 0.0) {
       swap_current_candidate(h);
       t0 = now_s();
-      radius = radius / std::max(1.0 / 3.0, 1.0 - std::pow(2.0 * rel - 1.0, 3));
-      radius = std::min(o.max_radius, radius);
-      decrease_factor = 2.0;
-      if (int rc = launch_sweep(h, radius)) return rc;
-      if (int rc = read_sweep_scalars(h, &x_cost, &gmax, &bad)) return rc;
-      if (o.precision == 1) x_cost = cand_cost;   // the fp64 cost of the point just accepted (see cost64_current)
+      if (int rc = launch_sweep(h, lm[LM_RADIUS])) return rc;
+      if (int rc = read_sweep_scalars(h, &cost, &gmax, &bad)) return rc;
+      lm_take_sweep(lm, lo, o.precision == 1 ? cand_cost : cost, gmax, bad);   // (precision = 1: the fp64 cost of the point just accepted, see cost64_current)
       s->seconds_sweep += now_s() - t0;
-      system_ready = true; step_successful = true; ++s->successful_steps;
-    } else {
-      radius = radius / decrease_factor; decrease_factor *= 2.0; step_successful = false; ++s->unsuccessful_steps;
     }
-    if (o.verbose) printf("%4d % .6e   % .2e %10.2e  %9.2e  %9.2e %9.2e\n", iteration, x_cost, cost_change, gmax, step_norm, rel, radius);
+    if (o.verbose) printf("%4d % .6e   % .2e %10.2e  %9.2e  %9.2e %9.2e\n", iteration, lm[LM_X_COST], lm[LM_LAST_CHANGE], lm[LM_GMAX], lm[LM_LAST_STEP], lm[LM_LAST_REL], lm[LM_RADIUS]);
   }
-  if (h->trace) fprintf(stderr, "[lifcal_ba r%d] done: it %d termination %d cost %.17g\n", o.rank, iteration, (int)s->termination, x_cost);
+  if (h->trace) fprintf(stderr, "[lifcal_ba r%d] done: it %d termination %d cost %.17g\n", o.rank, (int)lm[LM_ITER], (int)lm[LM_TERMINATION], lm[LM_X_COST]);
   if (int rc = download_parameters(h)) return rc;
-  s->iterations = iteration; s->final_cost = x_cost; s->final_radius = radius; s->final_gradient_max_norm = gmax;
+  lm_fill_summary(lm, s);
   s->seconds_total = now_s() - t_start;
   return 0;
-}
-
-void lifcal_ba_default_covariance_options(lifcal_ba_covariance_options* o) {
-  if (!o) return;
-  o->gauge_frame = -1; o->want_pose_blocks = 1; o->scale_by_residual_variance = 0; o->reserved = 0;
-  o->null_rcond = 1e-9; o->estimable_tol = 1e-3;
-}
-
-// sweep at radius = infinity (no damping anywhere: clamp(..) / (inf s^2) = 0, on the point blocks U_p too),
-// K1 chain -> C, K2 / K3 on the factor, C+ on the host, K4.  The handle's state is put back before returning, on every path.
-int lifcal_ba_covariance(lifcal_ba_handle* h, const lifcal_ba_covariance_options* oin, lifcal_ba_covariance_out* out) {
-  if (!h || !out || !out->camera) { g_last_error = "lifcal_ba_covariance: null handle, output or output->camera"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  lifcal_ba_covariance_options o; if (oin) o = *oin; else lifcal_ba_default_covariance_options(&o);
-  Dev& d = h->d;
-  const uint32_t F = d.F, NA = d.NA, Q3 = 3 * d.Q, nc = d.nc;
-  if (h->opt.world_size > 1) { g_last_error = "lifcal_ba_covariance: world_size > 1 is not supported (every rank holds the reduced system: a follow-up)"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (h->opt.precision != 0) { g_last_error = "lifcal_ba_covariance: options.precision = 1 is not supported; create a second fp64 handle at the solved parameters"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (!h->use_sweep3 || h->use_sweep4) { g_last_error = "lifcal_ba_covariance needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  const size_t lds2 = (size_t)cov_selinv_lds(d.bw) * 8, lds3 = (size_t)cov_backsolve_lds(d.bw, NA) * 8, lds4 = (size_t)6 * NA * 8;
-  if (!h->bandw_ok || lds2 > 160 * 1024 || lds3 > 160 * 1024 || lds4 > 64 * 1024) {
-    g_last_error = "lifcal_ba_covariance: the band window (" + std::to_string(d.bw + 1) + " frames, " + std::to_string(NA) + " arrow rows) does not fit LDS; only the LDS-window factorisation is supported";
-    return LIFCAL_BA_ERR_INVALID_ARG;
-  }
-  if (!(o.null_rcond >= 0.0) || !(o.estimable_tol >= 0.0) || o.gauge_frame < -2 || (o.gauge_frame >= 0 && (uint32_t)o.gauge_frame >= F)) {
-    g_last_error = "lifcal_ba_covariance: gauge_frame must be -2, -1 or a frame index; null_rcond and estimable_tol >= 0"; return LIFCAL_BA_ERR_INVALID_ARG;
-  }
-  // the gauge frame: held constant for this call only
-  const std::vector<uint8_t> live_saved = h->frame_live_host;
-  bool any_fixed = false;
-  for (uint32_t f = 0; f < F; ++f) if (h->plan.frame_used[f] && !live_saved[f]) any_fixed = true;
-  int32_t gauge = -1;
-  if (o.gauge_frame >= 0) {
-    if (!d.use_poses || !live_saved[o.gauge_frame]) { g_last_error = "lifcal_ba_covariance: the gauge frame must be an observed frame whose pose is refined"; return LIFCAL_BA_ERR_INVALID_ARG; }
-    gauge = o.gauge_frame;
-  } else if (o.gauge_frame == -1 && d.use_poses && d.use_points && !any_fixed) {
-    for (uint32_t f = 0; f < F; ++f) if (live_saved[f]) { gauge = (int32_t)f; break; }
-  }
-  HIP_TRY(hipSetDevice(h->opt.device));
-  HIP_TRY(hipStreamSynchronize(h->stream));
-  HIP_TRY(hipFuncSetAttribute((const void*)k_cov_selinv, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds2));
-  HIP_TRY(hipFuncSetAttribute((const void*)k_cov_backsolve, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds3));
-#define CA(ptr, n) do { if (!(ptr)) { if (int rc_ = dev_alloc(h, &(ptr), (n))) return rc_; } } while (0)
-  CA(h->cov_C, (size_t)NA * NA); CA(h->cov_Cp, (size_t)NA * NA); CA(h->cov_Zd, (size_t)std::max(1u, F) * 36); CA(h->cov_Y, (size_t)std::max(1u, F) * 6 * NA);
-  CA(h->cov_G, (size_t)std::max(1u, F) * 36); CA(h->cov_fail, 1);
-  if (out->pose_band && d.bw) CA(h->cov_Zb, (size_t)std::max(1u, F) * d.bw * 36);
-#undef CA
-  // what the call changes and puts back: the frame mask, the Jacobi scaling state, the device LM state, the profile span
-  const bool sigma_saved = h->sigma_valid, prof_saved = h->prof_on;
-  double lm_saved[LM_N];
-  HIP_TRY(hipMemcpy(lm_saved, d.lm, sizeof(lm_saved), hipMemcpyDeviceToHost));
-  auto restore = [&]() -> int {
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (F) HIP_TRY(hipMemcpy(h->frame_live_dev, live_saved.data(), F, hipMemcpyHostToDevice));
-    HIP_TRY(hipMemcpy(d.lm, lm_saved, sizeof(lm_saved), hipMemcpyHostToDevice));
-    h->sigma_valid = sigma_saved; h->prof_on = prof_saved;
-    return 0;
-  };
-  auto bail = [&](int rc) { const std::string e = g_last_error; restore(); g_last_error = e; return rc; };
-  h->prof_on = false;
-  if (gauge >= 0) {
-    std::vector<uint8_t> live(live_saved); live[gauge] = 0;
-    if (hipMemcpy(h->frame_live_dev, live.data(), F, hipMemcpyHostToDevice) != hipSuccess) { g_last_error = "lifcal_ba_covariance: frame mask upload failed"; return bail(LIFCAL_BA_ERR_HIP); }
-  }
-  // ---- the undamped reduced system, K1 .. K3 ----
-  if (hipEventRecord(h->ev0, h->stream) != hipSuccess) { g_last_error = "hipEventRecord failed"; return bail(LIFCAL_BA_ERR_HIP); }
-  if (int rc = launch_sweep(h, std::numeric_limits<double>::infinity())) return bail(rc);
-  hipLaunchKernelGGL(k_cov_chol_w, dim3(1), dim3(256), h->bandw_lds, h->stream, d, h->Lpanel, h->cov_C, h->cov_fail);
-  hipLaunchKernelGGL(k_cov_backsolve, dim3(1), dim3(256), lds3, h->stream, d, (const double*)h->Lpanel, h->cov_Y);
-  const bool want_pose = d.use_poses && (o.want_pose_blocks || out->pose_band);
-  if (want_pose) hipLaunchKernelGGL(k_cov_selinv, dim3(1), dim3(256), lds2, h->stream, d, (const double*)h->Lpanel, h->cov_Zd, out->pose_band && d.bw ? h->cov_Zb : nullptr);
-  if (hipGetLastError() != hipSuccess) { g_last_error = "lifcal_ba_covariance: kernel launch failed"; return bail(LIFCAL_BA_ERR_HIP); }
-  double cost, gmax, bad;
-  if (int rc = read_sweep_scalars(h, &cost, &gmax, &bad)) return bail(rc);
-  std::vector<double> C((size_t)NA * NA);
-  double failv = 0.0;
-  if (hipMemcpy(C.data(), h->cov_C, C.size() * 8, hipMemcpyDeviceToHost) != hipSuccess || hipMemcpy(&failv, h->cov_fail, 8, hipMemcpyDeviceToHost) != hipSuccess) {
-    g_last_error = "lifcal_ba_covariance: read-back failed"; return bail(LIFCAL_BA_ERR_HIP);
-  }
-  if (!std::isfinite(cost)) { g_last_error = "lifcal_ba_covariance: non-finite cost at the stored parameters"; return bail(LIFCAL_BA_ERR_NUMERIC); }
-  if (failv != 0.0) {
-    g_last_error = "lifcal_ba_covariance: the pose block of frame " + std::to_string((long long)failv - 1) + " is not positive definite after elimination: the data do not pin that frame down";
-    return bail(LIFCAL_BA_ERR_NUMERIC);
-  }
-  // ---- C+ on the live arrow slots (promoted points, free camera slots), Jacobi-scaled ----
-  CamConsts cc;
-  if (hipMemcpy(&cc, d.camc, sizeof(cc), hipMemcpyDeviceToHost) != hipSuccess) { g_last_error = "lifcal_ba_covariance: read-back failed"; return bail(LIFCAL_BA_ERR_HIP); }
-  std::vector<uint32_t> la;   // live arrow rows
-  for (uint32_t a = 0; a < NA; ++a) if (a < Q3 || cc.chm[a - Q3] != 0.0) la.push_back(a);
-  const uint32_t n = (uint32_t)la.size();
-  std::vector<double> sc(n), Cs((size_t)n * n), w, V;
-  for (uint32_t i = 0; i < n; ++i) { const double c = C[(size_t)la[i] * NA + la[i]]; sc[i] = c > 0.0 ? 1.0 / std::sqrt(c) : 1.0; }
-  for (uint32_t i = 0; i < n; ++i)
-    for (uint32_t k = 0; k < n; ++k) Cs[(size_t)i * n + k] = 0.5 * (C[(size_t)la[i] * NA + la[k]] + C[(size_t)la[k] * NA + la[i]]) * sc[i] * sc[k];
-  sym_eig_jacobi(n, Cs, w, V);
-  double wmax = 0.0;
-  for (double x : w) wmax = std::max(wmax, x);
-  std::vector<uint32_t> nulls;
-  for (uint32_t i = 0; i < n; ++i) if (!(w[i] > o.null_rcond * wmax)) nulls.push_back(i);
-  std::sort(nulls.begin(), nulls.end(), [&](uint32_t x, uint32_t y) { return w[x] < w[y]; });
-  std::vector<double> Cp((size_t)NA * NA, 0.0);
-  for (uint32_t i = 0; i < n; ++i)
-    for (uint32_t k = 0; k < n; ++k) {
-      double s = 0.0;
-      for (uint32_t e = 0; e < n; ++e) if (w[e] > o.null_rcond * wmax) s += V[(size_t)i * n + e] * V[(size_t)k * n + e] / w[e];
-      Cp[(size_t)la[i] * NA + la[k]] = s * sc[i] * sc[k];
-    }
-  // ---- units: residual variance over the rank of H ----
-  uint64_t n_free = 0, n_pts = 0;
-  for (uint32_t f = 0; f < F; ++f) if (d.use_poses && live_saved[f]) n_free += 6;
-  if (d.use_points) for (uint32_t q = 0; q < d.P; ++q) if (h->plan.point_used[q]) ++n_pts;
-  n_free += 3 * n_pts;
-  uint32_t live_mask = 0;
-  for (uint32_t j = 0; j < nc; ++j) if (cc.chm[j] != 0.0) { live_mask |= 1u << j; ++n_free; }
-  const uint64_t m = 2 * (uint64_t)h->plan.n_obs_local + d.M_local;
-  const double r = (double)n_free - (gauge >= 0 ? 6.0 : 0.0) - (double)nulls.size();
-  const double sigma2 = (double)m > r ? 2.0 * cost / ((double)m - r) : std::numeric_limits<double>::quiet_NaN();
-  const double mult = o.scale_by_residual_variance ? sigma2 : 1.0;
-  // ---- K4 ----
-  if (want_pose && o.want_pose_blocks && out->pose) {
-    if (hipMemcpyAsync(h->cov_Cp, Cp.data(), Cp.size() * 8, hipMemcpyHostToDevice, h->stream) != hipSuccess) { g_last_error = "lifcal_ba_covariance: upload failed"; return bail(LIFCAL_BA_ERR_HIP); }
-    hipLaunchKernelGGL(k_cov_combine, dim3(F), dim3(64), lds4, h->stream, d, (const double*)h->cov_Zd, (const double*)h->cov_Y, (const double*)h->cov_Cp, mult, h->cov_G);
-    if (hipGetLastError() != hipSuccess) { g_last_error = "lifcal_ba_covariance: kernel launch failed"; return bail(LIFCAL_BA_ERR_HIP); }
-  }
-  if (hipEventRecord(h->ev1, h->stream) != hipSuccess || hipStreamSynchronize(h->stream) != hipSuccess) { g_last_error = "lifcal_ba_covariance: device failure"; return bail(LIFCAL_BA_ERR_HIP); }
-  float ms = 0.f;
-  (void)hipEventElapsedTime(&ms, h->ev0, h->ev1);
-  // ---- outputs ----
-  std::fill(out->camera, out->camera + 17 * 17, 0.0);
-  for (uint32_t i = 0; i < nc; ++i)
-    for (uint32_t k = 0; k < nc; ++k) out->camera[i * 17 + k] = mult * Cp[(size_t)(Q3 + i) * NA + Q3 + k];
-  uint32_t est = 0;
-  for (uint32_t i = 0; i < n; ++i) {
-    if (la[i] < Q3) continue;
-    bool e = true;
-    for (uint32_t k : nulls) if (std::fabs(V[(size_t)i * n + k]) > o.estimable_tol) e = false;
-    if (e) est |= 1u << (la[i] - Q3);
-  }
-  if (out->camera_null) {
-    std::fill(out->camera_null, out->camera_null + 17 * 17, 0.0);
-    for (size_t r2 = 0; r2 < nulls.size() && r2 < 17; ++r2) {
-      double nrm = 0.0;   // the null direction in parameter units (unscaled), unit length over the live arrow slots
-      for (uint32_t i = 0; i < n; ++i) { const double v = V[(size_t)i * n + nulls[r2]] * sc[i]; nrm += v * v; }
-      nrm = nrm > 0.0 ? 1.0 / std::sqrt(nrm) : 0.0;
-      for (uint32_t i = 0; i < n; ++i) if (la[i] >= Q3) out->camera_null[r2 * 17 + (la[i] - Q3)] = V[(size_t)i * n + nulls[r2]] * sc[i] * nrm;
-    }
-  }
-  if (out->pose) {
-    if (want_pose && o.want_pose_blocks && F) { if (hipMemcpy(out->pose, h->cov_G, (size_t)F * 36 * 8, hipMemcpyDeviceToHost) != hipSuccess) { g_last_error = "lifcal_ba_covariance: read-back failed"; return bail(LIFCAL_BA_ERR_HIP); } }
-    else std::fill(out->pose, out->pose + (size_t)F * 36, 0.0);
-  }
-  if (out->pose_band && d.bw) {
-    std::vector<double> zb((size_t)F * d.bw * 36, 0.0);
-    if (want_pose && hipMemcpy(zb.data(), h->cov_Zb, zb.size() * 8, hipMemcpyDeviceToHost) != hipSuccess) { g_last_error = "lifcal_ba_covariance: read-back failed"; return bail(LIFCAL_BA_ERR_HIP); }
-    for (uint32_t f = 0; f < F; ++f)   // blocks past the last frame and blocks of frames that are not columns: zero
-      for (uint32_t dd = 1; dd <= d.bw; ++dd) {
-        const bool ok = f + dd < F && d.use_poses && live_saved[f] && live_saved[f + dd] && (int32_t)f != gauge && (int32_t)(f + dd) != gauge;
-        for (uint32_t e = 0; e < 36; ++e) out->pose_band[((size_t)f * d.bw + dd - 1) * 36 + e] = ok ? mult * zb[((size_t)f * d.bw + dd - 1) * 36 + e] : 0.0;
-      }
-  }
-  out->estimable_mask = est; out->null_rank = (uint32_t)nulls.size(); out->gauge_frame_used = gauge; out->live_mask = live_mask;
-  out->sigma2 = sigma2; out->cost = cost; out->seconds = ms * 1e-3;
-  return restore();
 }
 
 int lifcal_ba_reproj_stats(lifcal_ba_handle* h, double thr, lifcal_ba_stats* out) {
@@ -1694,6 +1438,9 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 
 // frame-windowed solve for long sequences (include/lifcal_ba.h)
 #include "windowed.hpp"
+
+// covariance of the calibrated parameters: kernels and lifcal_ba_covariance (include/lifcal_ba.h)
+#include "covariance.hpp"
 
 // depth-map sampling, back-projection to metric 3D and the object-space comparison (include/lifcal_depth.h, include/lifcal_ba.h)
 #include "depth.hpp"

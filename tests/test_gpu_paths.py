@@ -232,3 +232,30 @@ def test_block_odd_even_reduction_equals_the_chain(built, monkeypatch, spec):
     so = oracle.solve(pb, threads=4)
     assert (s1.iterations, s1.termination) == (so.iterations, so.termination)
     assert abs(s1.final_cost - so.final_cost) <= 1e-8 * so.final_cost
+
+
+@pytest.mark.parametrize("spec", [S(6, 40, None, 0x006, 113), S(6, 40, None, 0x506, 117, n_constraints=3)],
+                         ids=["camera_only_function_tolerance_after_rejected_steps", "distance_constraints"])
+def test_host_and_device_lm_loops_decide_alike(built, monkeypatch, spec):
+    """the host loop of lifcal_ba_solve (LIFCAL_HOST_LM=1) and k_lm_control call the same functions of lm_step.hpp on the scalars of
+    the same kernels: with ordered sums (options.deterministic = 1) the two routes take the same trajectory to the last bit.  The
+    first problem rejects eight of its sixteen steps before the function tolerance ends it (oracle: 16 / 7 / 8)."""
+    sc = scene.make_scene(spec)
+    res = {}
+    for route in ("device", "host"):
+        if route == "host":
+            monkeypatch.setenv("LIFCAL_HOST_LM", "1")
+        else:
+            monkeypatch.delenv("LIFCAL_HOST_LM", raising=False)
+        pa = problem(sc)
+        with BundleAdjustment(pa, ordered()) as ba:
+            s = ba.performBundleAdjustment()
+        res[route] = (pa, s)
+    (pd, sd), (ph, sh) = res["device"], res["host"]
+    print("device", sd.iterations, sd.successful_steps, sd.unsuccessful_steps, sd.termination, repr(sd.final_radius), repr(sd.final_cost))
+    print("host  ", sh.iterations, sh.successful_steps, sh.unsuccessful_steps, sh.termination, repr(sh.final_radius), repr(sh.final_cost))
+    assert (sh.iterations, sh.successful_steps, sh.unsuccessful_steps, sh.termination) == (sd.iterations, sd.successful_steps, sd.unsuccessful_steps, sd.termination)
+    if spec.n_constraints == 0:
+        assert sd.termination == 1 and sd.unsuccessful_steps >= 3   # LIFCAL_BA_TERM_FUNCTION_TOLERANCE, several rejected steps
+    assert sh.final_radius == sd.final_radius and sh.final_cost == sd.final_cost
+    assert np.array_equal(ph.cam, pd.cam) and np.array_equal(ph.views, pd.views) and np.array_equal(ph.pts, pd.pts)
