@@ -204,7 +204,7 @@ typedef struct lifcal_ba_profile {
                              camera-only / pose-only arities); their time is part of ms_schur, NOT of ms_accumulate        */
   double ms_accumulate;   /* the dominant kernel of the regular points by its own dispatch time stamps: k_sweep3 (fused residual +
                              Jacobian + accumulation + point elimination), or k_front4 start to k_back4 end                */
-  double ms_schur;        /* ms_total - ms_accumulate: tables, special points, constraints, exchange, k_finalize, gaps  */
+  double ms_schur;        /* ms_total - ms_accumulate: special points, constraints, exchange, k_finalize, gaps (tables: only where the parameters changed) */
   double ms_total;        /* first kernel of the first sweep to the end of the last one, divided by the sweep count    */
   double ms_exchange;     /* world_size > 1: pack + collective + unpack of the partial reduced blocks (part of ms_schur)  */
   uint32_t n_sampled;     /* sweeps of the span whose dominant kernel carried the time stamps (ms_accumulate / ms_exchange average THESE) */

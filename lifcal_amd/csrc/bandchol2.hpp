@@ -283,7 +283,7 @@ __global__ __launch_bounds__(256) void k_band_chol_seg(Dev d, double* Lpanel, Ba
     }
     double* daa = da + (size_t)NAx * nt * 6;
     for (uint32_t t = lane; t < NAx * NAx; t += 256) { const uint32_t a = t / NAx, b = t % NAx; daa[t] = b <= a ? Wd[(size_t)(arow0 + a) * nw + arow0 + b] : 0.0; }
-    if (lane == 0 && *failp != 0.0) d.step[ST_CHOL_FAIL] = 1.0;   // (zeroed by k_tables; both chains and the final one may only raise it)
+    if (lane == 0 && *failp != 0.0) d.step[ST_CHOL_FAIL] = 1.0;   // (zeroed with the block the sweep accumulated into; both chains and the final one may only raise it)
     return;
   }
   // ---- dense Cholesky of the arrow block (NA x NA), rhs row carried along ----

@@ -1,13 +1,13 @@
 // kernels.hpp — gfx950 kernels of the bundle-adjustment hot path (wave64, fp64).
 //
 // Sweep = what ceres does per LM iteration for the reference:
-//   k_tables      camera constants, frame table, lens table          (hoisted out of the per-obs functor)
+//   k_tables      camera constants, frame table, lens table          (hoisted out of the per-obs functor; once per parameter set)
 //   k_sweep       residual + analytic Jacobian per observation, robust weights (CauchyLoss(0.5),
 //                 reference src/CameraCalibration.cpp:892), and the block accumulation
 //                 U_p, g_p, W_p (point blocks) and B, g_B (camera+pose blocks)
 //   k_constraints distance constraints (reference BundleAdjustment.h:255-279)
 //   k_schur       U_p + D_p -> inverse; S -= W^T U^-1 W ; rhs += W^T U^-1 g   (ceres SchurEliminator)
-//   k_finalize    LM diagonal on the reduced system, rhs, identity on fixed columns
+//   k_finalize    LM diagonal on the reduced system, rhs, identity on fixed columns; zero-fill of the next sweep's block
 //   k_band_chol / k_band_backsolve   block-banded + arrow Cholesky of S (ceres DenseSchurComplementSolver)
 //   k_update_reduced / k_backsub     step for camera+poses, back-substitution for points, candidate point
 //   k_cost        candidate cost ; k_stats reprojection statistics (reference :1026-1103)
@@ -169,13 +169,14 @@ __global__ void k_lenses(const CamConsts* camc, const double* lens_xy, double* l
   for (int k = 0; k < LENS_STRIDE; ++k) lt[(size_t)l * LENS_STRIDE + k] = o[k];
 }
 
-// one launch for everything that precedes a sweep: camera constants (recomputed by every thread: ~100 flops, no
-// dependency on another kernel), lens table, frame table, and zero-filling of the accumulation buffers
+// one launch for the tables of a parameter set: camera constants (recomputed by every thread: ~100 flops, no
+// dependency on another kernel), lens table, frame table.  Launched where a parameter set is new (the host keeps the record:
+// sweep_state.hpp), not in front of every sweep
 template <int NR, bool TAN>
 __global__ __launch_bounds__(256) void k_tables(Dev d, const double* cam, const double* views, CamConsts* camc_out, double* ft, double* lt,
-                                                const double* lens_xy, int want_tangents, int fold, double* zero0, uint32_t n_zero0, double* zero1, uint32_t n_zero1,
+                                                const double* lens_xy, int want_tangents, int fold,
                                                 float* ltf /* fp32 lens table (options.precision = 1) or null */) {
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, nthreads = gridDim.x * blockDim.x;
+  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   CamConsts c;
   cam_prepare(cam, d.spx, d.spy, fold ? d.scale : (double)(float)d.scale, (int)d.n_radial, d.tangential != 0, d.fixed_mask, d.loss_scale, fold != 0, c);
   if (t == 0) *camc_out = c;
@@ -199,8 +200,6 @@ __global__ __launch_bounds__(256) void k_tables(Dev d, const double* cam, const 
 #pragma unroll
     for (int k = 0; k < FRAME_STRIDE; ++k) ft[(size_t)t * FRAME_STRIDE + k] = o[k];
   }
-  for (uint32_t i = t; i < n_zero0; i += nthreads) zero0[i] = 0.0;
-  for (uint32_t i = t; i < n_zero1; i += nthreads) zero1[i] = 0.0;
 }
 
 // point slabs of the special points (the v1 kernels accumulate into them with atomics)
@@ -817,7 +816,15 @@ __global__ void k_det_sum(const double* slots, uint32_t n_wg, uint32_t K, double
 // ---------------------------------------------------------------------------------------------
 // finalize: LM diagonal on the reduced system + rhs row; identity on columns that are not solved for
 // ---------------------------------------------------------------------------------------------
-__global__ void k_finalize(Dev d, double radius) {
+// Workgroups from n_fin on do something else, beside the finalising ones: they zero-fill `zero` (the copy of the reduced block
+// and step scalars that the NEXT sweep accumulates into; nobody reads it any more)
+constexpr uint32_t FIN_ZERO_PER_WG = 256 * 4;   // doubles per zero-filling workgroup the host sizes the grid with
+__global__ void k_finalize(Dev d, double radius, uint32_t n_fin, double* zero, uint32_t n_zero) {
+  if (blockIdx.x >= n_fin) {
+    const uint32_t n_threads = (gridDim.x - n_fin) * blockDim.x;
+    for (uint32_t i = (blockIdx.x - n_fin) * blockDim.x + threadIdx.x; i < n_zero; i += n_threads) zero[i] = 0.0;
+    return;
+  }
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
   if (t == 0) d.lm[LM_T0] = (double)__builtin_amdgcn_s_memrealtime();   // the linear solve starts here (k_lm_control reads the span: no event records in the device loop)
   double g = 0.0;
@@ -1244,13 +1251,19 @@ __global__ void k_lm_control(Dev d, LmOpts o, const double* partial, double* mir
   *(volatile double*)(mirror + LM_SEQ) = seq;
 }
 
-// an accepted candidate becomes the current point (the host loop swaps pointers; device code keeps its arguments and copies)
+// an accepted candidate becomes the current point (the host loop swaps pointers; device code keeps its arguments and copies),
+// and the candidate's tables (built with tangents for k_cost one kernel earlier) the current tables: the sweep behind this kernel
+// needs no table build whichever way the decision went
+static_assert(sizeof(CamConsts) % sizeof(double) == 0, "k_lm_commit copies CamConsts as doubles");
 __global__ void k_lm_commit(Dev d) {
   if (d.lm[LM_COMMIT] == 0.0) return;
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x, n = gridDim.x * blockDim.x;
   for (uint32_t i = t; i < LIFCAL_BA_MAX_CAMERA_PARAMETERS; i += n) d.cam[i] = d.cam_c[i];
   for (uint32_t i = t; i < 6 * d.F; i += n) d.views[i] = d.views_c[i];
   if (d.use_points) for (uint32_t i = t; i < 3 * d.P; i += n) d.pts[i] = d.pts_c[i];
+  for (uint32_t i = t; i < sizeof(CamConsts) / sizeof(double); i += n) ((double*)d.camc)[i] = ((const double*)d.camc_c)[i];
+  for (uint32_t i = t; i < d.F * (uint32_t)FRAME_STRIDE; i += n) d.ft[i] = d.ft_c[i];
+  for (uint32_t i = t; i < d.n_lenses * (uint32_t)LENS_STRIDE; i += n) d.lt[i] = d.lt_c[i];
 }
 
 // ---------------------------------------------------------------------------------------------

@@ -25,6 +25,7 @@
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "linesearch.hpp"
+#include "sweep_state.hpp"
 
 using namespace lifcal;
 
@@ -107,7 +108,9 @@ struct lifcal_ba_handle {
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   std::vector<void*> allocs;
   uint64_t bytes = 0;
-  double* red_block = nullptr; size_t red_count = 0;
+  double* red_block = nullptr; size_t red_count = 0;   // the copy of the reduced block Dev points at (bind_block)
+  double* red_blocks[2] = {nullptr, nullptr};          // block | step scalars | candidate partial sums, twice: a sweep fills the copy the previous one left
+  SweepState ss;                 // which parameters the table sets belong to, which copy of the block is zero (sweep_state.hpp)
   size_t v2_lds_bytes = 0;
   bool use_sweep3 = true;        // wave-specialised LDS-window kernel (LIFCAL_SWEEP_KERNEL=2 selects k_sweep2)
   int sweep_waves = 4;           // k_sweep3: waves per role, 4 (512 threads, 256-lane passes) or 2 (256 threads, 128-lane passes, two workgroups per CU)
@@ -141,7 +144,7 @@ struct lifcal_ba_handle {
   double* Lpanel = nullptr; size_t bandw_lds = 0, backw_lds = 0; bool bandw_ok = false;
   CrPlan cr; bool use_cr = false;   // block odd-even reduction (bandchol3.hpp): long sequences
   bool twisted = false; uint32_t tw_m = 0; double *dumpA = nullptr, *dumpB = nullptr;   // two-ended factorisation (bandchol2.hpp): frames [0, tw_m) | bw middle frames | the rest
-  // profiling: 5 events per sweep (start, after tables, after k_sweep, before k_schur, after k_schur, end)
+  // profiling: events per sampled sweep ([1], [2]: the dominant kernel's own stamps; [3], [4]: around the exchange)
   // A profile spans prof_cap sweeps (two records: before the first, behind the last); every prof_stride-th sweep of the span is
   // SAMPLED: its dominant kernel carries its own start / stop events — which costs ~5 us of queue time per sampled sweep, so a
   // timing loop samples a few of its sweeps rather than all of them (lifcal_ba_profile_begin_sampled)
@@ -237,16 +240,54 @@ uint32_t sweep_grid(const lifcal_ba_handle* h) {
   return std::max(1u, std::min(wgs, 2048u));
 }
 
-// tables for a parameter set (camera constants, frames, lenses) + zero-fill of up to two buffers, ONE launch
-int launch_tables(lifcal_ba_handle* h, const double* cam, const double* views, CamConsts* camc, double* ft, double* lt, bool tangents, bool fold,
-                  double* zero0 = nullptr, size_t n_zero0 = 0, double* zero1 = nullptr, size_t n_zero1 = 0, float* ltf = nullptr) {
+// tables for a parameter set (camera constants, frames, lenses), ONE launch
+int launch_tables(lifcal_ba_handle* h, const double* cam, const double* views, CamConsts* camc, double* ft, double* lt, bool tangents, bool fold, float* ltf = nullptr) {
   const Dev& d = h->d;
-  const uint32_t work = std::max<uint32_t>(std::max(d.n_lenses, d.F), (uint32_t)std::min<size_t>((n_zero0 + n_zero1 + 7) / 8, 1u << 20));
-  const uint32_t grid = std::max(1u, (work + 255) / 256);
-#define CALL_TABLES(NR, TAN) hipLaunchKernelGGL((k_tables<NR, TAN>), dim3(grid), dim3(256), 0, h->stream, d, cam, views, camc, ft, lt, (const double*)h->lens_xy, tangents ? 1 : 0, fold ? 1 : 0, zero0, (uint32_t)n_zero0, zero1, (uint32_t)n_zero1, ltf)
+  const uint32_t grid = std::max(1u, (std::max(d.n_lenses, d.F) + 255) / 256);
+#define CALL_TABLES(NR, TAN) hipLaunchKernelGGL((k_tables<NR, TAN>), dim3(grid), dim3(256), 0, h->stream, d, cam, views, camc, ft, lt, (const double*)h->lens_xy, tangents ? 1 : 0, fold ? 1 : 0, ltf)
   DISPATCH_LENS(h, CALL_TABLES);
 #undef CALL_TABLES
   HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// the table sets as state of a parameter set (sweep_state.hpp keeps the record, these three are the only writers of the sets
+// the solver reads): the current set is built when the record says it is not that of d.cam / d.views with tangents, folded ...
+int ensure_current_tables(lifcal_ba_handle* h) {
+  Dev& d = h->d;
+  if (!ss_sweep_needs_tables(&h->ss)) return 0;
+  if (int rc = launch_tables(h, d.cam, d.views, d.camc, d.ft, d.lt, true, true, d.ltf)) return rc;
+  ss_tables_built(&h->ss, SS_CURRENT, SS_CURRENT, true, true);
+  return 0;
+}
+// ... the candidate set with tangents as well: after an accepted step it IS the current set of the next sweep
+int build_candidate_tables(lifcal_ba_handle* h) {
+  Dev& d = h->d;
+  if (int rc = launch_tables(h, d.cam_c, d.views_c, d.camc_c, d.ft_c, d.lt_c, true, true)) return rc;
+  ss_tables_built(&h->ss, SS_CANDIDATE, SS_CANDIDATE, true, true);
+  return 0;
+}
+// ... and calcReprojectionError / projectObservations borrow the candidate arrays for unfolded tables of the current point
+int build_stats_tables(lifcal_ba_handle* h) {
+  Dev& d = h->d;
+  ss_tables_clobbered(&h->ss, SS_CANDIDATE);
+  return launch_tables(h, d.cam, d.views, h->camc_stats, d.ft_c, d.lt_c, false, false);
+}
+
+// Dev and h->red_block point at copy `which` of the reduced block; nothing else knows that there are two
+void bind_block(lifcal_ba_handle* h, int which) {
+  Dev& d = h->d;
+  const size_t n_band = (size_t)d.F * (d.bw + 1) * 36, n_arrow = (size_t)(d.NA + 1) * d.ld;
+  h->red_block = h->red_blocks[which];
+  d.Sband = h->red_block; d.Sarrow = d.Sband + n_band; d.rhsacc = d.Sarrow + n_arrow; d.gB = d.rhsacc + d.n_red; d.hdiag = d.gB + d.n_red; d.scal = d.hdiag + d.n_red;
+  d.step = d.scal + SCAL_N; h->partial = d.step + ST_N;   // (behind the all-reduced block, not part of it)
+}
+// a zero block and zero step scalars to accumulate into: the copy the previous accumulation did not use.  The k_finalize of a
+// sweep leaves it zero-filled; behind anything else (first sweep, diagonal-only pass, trial sweeps of the line search) it is filled here
+int acquire_block(lifcal_ba_handle* h) {
+  const bool fill = ss_acquire_block(&h->ss);
+  bind_block(h, h->ss.bound);
+  if (fill) HIP_TRY(hipMemsetAsync(h->red_block, 0, (h->red_count + ST_N) * sizeof(double), h->stream));
   return 0;
 }
 
@@ -273,9 +314,9 @@ int launch_value_cost(lifcal_ba_handle* h, const CamConsts* camc, const double* 
 }
 
 // the kernels that turn observations into blocks.  mode 1 = Hessian diagonal only (Jacobi scaling, iteration 0)
-int launch_blocks(lifcal_ba_handle* h, double radius, int mode, bool zeroed) {
+int launch_blocks(lifcal_ba_handle* h, double radius, int mode) {
+  if (int rc = acquire_block(h)) return rc;
   Dev& d = h->d;
-  if (!zeroed) HIP_TRY(hipMemsetAsync(h->red_block, 0, h->red_count * sizeof(double), h->stream));
   if (d.n_special) hipLaunchKernelGGL(k_zero_special, dim3((d.n_special * 36 + 255) / 256), dim3(256), 0, h->stream, d);
   if (d.deterministic && (d.n_tiles || d.n_special)) HIP_TRY(hipMemsetAsync(d.det_turn, 0, 4 * sizeof(uint32_t), h->stream));   // turn counters of k_sweep / k_schur
   // profiling: the dominant kernel carries its own start / stop events (hipExtLaunchKernelGGL: the time stamps are written by the
@@ -331,14 +372,11 @@ int launch_blocks(lifcal_ba_handle* h, double radius, int mode, bool zeroed) {
 int launch_sweep(lifcal_ba_handle* h, double radius) {
   Dev& d = h->d;
   if (h->prof_in_span() && h->prof_seen == 0) HIP_TRY(hipEventRecord(h->prof_span0, h->stream));   // the span opens with the first profiled sweep ...
-  // the table kernel also zero-fills the reduced block and the step scalars
-  if (int rc = launch_tables(h, d.cam, d.views, d.camc, d.ft, d.lt, true, true, h->red_block, h->red_count, d.step, ST_N, d.ltf)) return rc;
-  bool zeroed = true;
+  if (int rc = ensure_current_tables(h)) return rc;
   if (!h->sigma_valid) {
     // ceres fixes the Jacobi scaling at iteration 0 from the column norms of the (loss-corrected) Jacobian:
     // a diagonal-only pass, then 1 / (1 + sqrt(diag)) for every column
-    if (int rc = launch_blocks(h, radius, 1, zeroed)) return rc;
-    zeroed = false;
+    if (int rc = launch_blocks(h, radius, 1)) return rc;
     const double* hd = d.hdiag;
     if (h->opt.world_size > 1) {
       HIP_TRY(hipMemcpyAsync(h->hdiag_tmp, d.hdiag, d.n_red * sizeof(double), hipMemcpyDeviceToDevice, h->stream));
@@ -351,7 +389,7 @@ int launch_sweep(lifcal_ba_handle* h, double radius) {
     HIP_TRY(hipGetLastError());
     h->sigma_valid = true;
   }
-  if (int rc = launch_blocks(h, radius, 0, zeroed)) return rc;
+  if (int rc = launch_blocks(h, radius, 0)) return rc;
   if (d.use_points && d.n_special) hipLaunchKernelGGL(k_schur, dim3((d.n_special + 3) / 4), dim3(256), 0, h->stream, d, radius);
   HIP_TRY(hipGetLastError());
   {
@@ -362,8 +400,16 @@ int launch_sweep(lifcal_ba_handle* h, double radius) {
     if (int rc = exchange_reduced(h)) return rc;
     if (prof_x) HIP_TRY(hipEventRecord(h->prof_ev(4), h->stream));
   }
-  hipLaunchKernelGGL(k_finalize, dim3((d.n_red + 255) / 256), dim3(256), 0, h->stream, d, radius);
-  HIP_TRY(hipGetLastError());
+  {
+    // extra workgroups, beside the finalising ones, zero-fill the OTHER copy of the block (and its step scalars) for the next sweep:
+    // its last readers were the consumers of the previous sweep, all in front of this one on the stream
+    const uint32_t n_fin = (d.n_red + 255) / 256;
+    const uint32_t n_zero = (uint32_t)(h->red_count + ST_N);
+    const uint32_t n_fill = std::min((n_zero + FIN_ZERO_PER_WG - 1) / FIN_ZERO_PER_WG, 1024u);
+    hipLaunchKernelGGL(k_finalize, dim3(n_fin + n_fill), dim3(256), 0, h->stream, d, radius, n_fin, h->red_blocks[h->ss.bound ^ 1], n_zero);
+    HIP_TRY(hipGetLastError());
+    ss_finalize_cleaned_other(&h->ss);
+  }
   if (h->prof_in_span()) {   // ... and closes with the last one (a record per sweep is a barrier packet per sweep)
     if (h->prof_seen + 1 == h->prof_cap) { HIP_TRY(hipEventRecord(h->prof_span1, h->stream)); h->prof_closed = true; }
     if (h->prof_active()) h->prof_used++;
@@ -422,7 +468,8 @@ int launch_candidate(lifcal_ba_handle* h) {
     if (d.deterministic) hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(64), 0, h->stream, (const double*)d.det_slots, (n + 255) / 256, 4u, h->partial);
   }
   HIP_TRY(hipGetLastError());
-  if (int rc = launch_tables(h, d.cam_c, d.views_c, d.camc_c, d.ft_c, d.lt_c, false, true)) return rc;
+  ss_candidate_written(&h->ss);
+  if (int rc = build_candidate_tables(h)) return rc;
   if (int rc = launch_value_cost(h, d.camc_c, d.ft_c, d.lt_c, d.use_points ? d.pts_c : d.pts, h->partial + 4)) return rc;
   return do_allreduce(h, h->partial, 8);
 }
@@ -439,10 +486,22 @@ int cost64_current(lifcal_ba_handle* h, double* cost) {
   return 0;
 }
 
+// the parameter pointers change places (line search: to sweep at a trial point and back); the table sets stay where they are
 void swap_current_candidate(lifcal_ba_handle* h) {
   Dev& d = h->d;
   std::swap(d.cam, d.cam_c); std::swap(d.views, d.views_c);
   if (d.use_points) std::swap(d.pts, d.pts_c);
+  ss_swap_parameters(&h->ss);
+}
+// host loop, accepted step: the candidate becomes the current point, its tables (launch_candidate / line_search built them with
+// tangents) the current tables.  options.precision = 1: the fp32 lens table has no candidate twin, the next sweep rebuilds the set
+void accept_candidate(lifcal_ba_handle* h) {
+  Dev& d = h->d;
+  const bool with_tables = h->opt.precision == 0;
+  std::swap(d.cam, d.cam_c); std::swap(d.views, d.views_c);
+  if (d.use_points) std::swap(d.pts, d.pts_c);
+  if (with_tables) { std::swap(d.camc, d.camc_c); std::swap(d.ft, d.ft_c); std::swap(d.lt, d.lt_c); }
+  ss_host_accept(&h->ss, with_tables);
 }
 
 // ---- Armijo line search (bounded problems) ---------------------------------------------------------------------
@@ -452,6 +511,7 @@ int launch_apply_step(lifcal_ba_handle* h, double t) {
   HIP_TRY(hipMemsetAsync(h->ls_buf, 0, 8 * sizeof(double), h->stream));
   const uint32_t n = std::max(std::max(6 * d.F, 17u), std::max(d.n_owned, d.Q));
   hipLaunchKernelGGL(k_apply_step, dim3((n + 255) / 256), dim3(256), 0, h->stream, d, t, h->ls_buf);
+  ss_candidate_written(&h->ss);
   if (d.deterministic) hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(64), 0, h->stream, (const double*)d.det_slots, (n + 255) / 256, 2u, h->ls_buf);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -463,8 +523,8 @@ int eval_trial(lifcal_ba_handle* h, double t, double radius, LsSample* smp) {
   Dev& d = h->d;
   if (int rc = launch_apply_step(h, t)) return rc;
   swap_current_candidate(h);
-  int rc = launch_tables(h, d.cam, d.views, d.camc, d.ft, d.lt, true, true, h->red_block, h->red_count, d.step, ST_N, d.ltf);
-  if (!rc) rc = launch_blocks(h, radius, 0, true);
+  int rc = ensure_current_tables(h);   // (at the trial point: the record sees the swap)
+  if (!rc) rc = launch_blocks(h, radius, 0);
   if (!rc && d.use_points && d.n_special) { hipLaunchKernelGGL(k_schur, dim3((d.n_special + 3) / 4), dim3(256), 0, h->stream, d, radius); }
   if (!rc) rc = do_allreduce(h, h->red_block, h->red_count);
   if (!rc) {
@@ -550,7 +610,7 @@ int line_search(lifcal_ba_handle* h, double x_cost, double g0, double radius, in
   const double t_opt = ls_ok ? cur.x : 1.0;
   if (int rc = launch_apply_step(h, t_opt)) return rc;
   HIP_TRY(hipMemsetAsync(h->partial, 0, 8 * sizeof(double), h->stream));
-  if (int rc = launch_tables(h, d.cam_c, d.views_c, d.camc_c, d.ft_c, d.lt_c, false, true)) return rc;
+  if (int rc = build_candidate_tables(h)) return rc;
   if (int rc = launch_value_cost(h, d.camc_c, d.ft_c, d.lt_c, d.use_points ? d.pts_c : d.pts, h->partial + 4)) return rc;
   if (int rc = do_allreduce(h, h->partial, 8)) return rc;
   if (int rc = do_allreduce(h, h->ls_buf, 2)) return rc;
@@ -580,6 +640,7 @@ int upload_parameters(lifcal_ba_handle* h) {
   if (d.P) { HIP_TRY(hipMemcpyAsync(d.pts, p.pts, 3 * (size_t)d.P * 8, hipMemcpyHostToDevice, h->stream));
              HIP_TRY(hipMemcpyAsync(d.pts_c, d.pts, 3 * (size_t)d.P * 8, hipMemcpyDeviceToDevice, h->stream)); }
   HIP_TRY(hipStreamSynchronize(h->stream));   // (cam is a stack array, the caller's arrays may change after the call)
+  ss_upload(&h->ss);
   h->sigma_valid = false;
   return 0;
 }
@@ -968,8 +1029,10 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
   }
   const size_t n_band = (size_t)d.F * (d.bw + 1) * 36, n_arrow = (size_t)(d.NA + 1) * d.ld;
   h->red_count = n_band + n_arrow + 3 * (size_t)d.n_red + SCAL_N;
-  A(h->red_block, h->red_count + ST_N + 8);   // ... | scal | step scalars | candidate partial sums: the host reads each pair with ONE copy
-  d.Sband = h->red_block; d.Sarrow = d.Sband + n_band; d.rhsacc = d.Sarrow + n_arrow; d.gB = d.rhsacc + d.n_red; d.hdiag = d.gB + d.n_red; d.scal = d.hdiag + d.n_red;
+  // ... | scal | step scalars | candidate partial sums: the host reads each pair with ONE copy.  Two copies, see acquire_block
+  A(h->red_blocks[0], h->red_count + ST_N + 8); A(h->red_blocks[1], h->red_count + ST_N + 8);
+  ss_reset(&h->ss);
+  bind_block(h, h->ss.bound);
   A(d.sig_red, d.n_red); A(d.lam_red, d.n_red); A(d.delta_red, d.n_red); A(d.Linv, (size_t)d.F * 36 + 36);
   // multi-GPU: slab exchange of the reduced block (every rank's partial block lives in one frame range)
   h->force_exchange = getenv("LIFCAL_FORCE_EXCHANGE") != nullptr;
@@ -991,7 +1054,6 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
   }
   A(d.dbg, std::max((size_t)std::max(1u, d.n_blocks) * 32, (size_t)d.n_fwg * 64));
   A(d.dP, 3 * (size_t)d.P); A(h->ls_buf, 8); A(h->dirmax_buf, 65); A(d.lm, LM_N);
-  d.step = d.scal + SCAL_N; h->partial = d.step + ST_N;   // (behind the all-reduced block, not part of it)
   A(h->hdiag_tmp, d.n_red); A(h->stats_buf, 8); A(h->stats_slots, 4 + 2 * 64); A(h->pts_gather, 3 * (size_t)d.P);
   // Cholesky panel: LDS when it fits (<= 64 KiB by default launch limits), else a global scratch
   const size_t panel_rows = 6 * (size_t)d.bw + d.NA + 1;
@@ -1166,7 +1228,7 @@ int lifcal_ba_profile_end(lifcal_ba_handle* h, lifcal_ba_profile* out) {
     out->ms_total = t / seen;
     if (n) { out->ms_accumulate /= n; out->ms_exchange /= n; }
     out->special_points = (double)h->d.n_special;           // (their kernels run outside the dominant kernel's time stamps)
-    out->ms_schur = out->ms_total - out->ms_accumulate;     // everything outside the dominant kernel: tables, finalize, special points, exchange, launch gaps
+    out->ms_schur = out->ms_total - out->ms_accumulate;     // everything outside the dominant kernel: finalize (with its zero-fill for the next sweep), special points, exchange, launch gaps; a table build only where the parameters changed
   }
   out->n_sweeps = seen;
   out->n_sampled = n;
@@ -1246,7 +1308,8 @@ static int solve_device_loop(lifcal_ba_handle* h, const LmOpts& lo, lifcal_ba_su
   HIP_TRY(hipMemcpyAsync(d.lm, h->h_lm + LM_N, LM_N * sizeof(double), hipMemcpyHostToDevice, h->stream));
   double t0 = now_s();
   if (int rc = launch_sweep(h, -1.0)) return rc;
-  const uint32_t commit_grid = std::max(1u, std::min(1024u, (3 * d.P + 6 * d.F + 255) / 256));
+  // (sized for the larger of its two copies: parameters, tables)
+  const uint32_t commit_grid = std::max(1u, std::min(1024u, (std::max(3 * d.P + 6 * d.F, (d.n_lenses + d.F) * (uint32_t)LENS_STRIDE) + 255) / 256));
   volatile double* mirror = h->h_lm;
   mirror[LM_SEQ] = 0.0;
   for (int round = 0; round < o.max_iterations + 8; ++round) {
@@ -1255,6 +1318,7 @@ static int solve_device_loop(lifcal_ba_handle* h, const LmOpts& lo, lifcal_ba_su
     hipLaunchKernelGGL(k_lm_control, dim3(1), dim3(64), 0, h->stream, d, lo, (const double*)h->partial, h->h_lm_dev, (double)(round + 1));
     hipLaunchKernelGGL(k_lm_commit, dim3(commit_grid), dim3(256), 0, h->stream, d);
     HIP_TRY(hipGetLastError());
+    ss_device_commit(&h->ss);
     if (int rc = launch_sweep(h, -1.0)) return rc;         // speculative: runs while the host looks at the state
     // wait for this round's state: one word of mapped host memory, written last by k_lm_control.  A queue that died would never
     // write it: every ~2 ms of waiting the stream is asked for its status (an error ends the wait, "not ready" continues it)
@@ -1327,7 +1391,7 @@ int lifcal_ba_solve(lifcal_ba_handle* h, lifcal_ba_summary* s) {
     lm_judge_step(lm, lo, cand_cost, step2, x2);
     if (lm[LM_TERMINATION] != 0.0) break;
     if (lm[LM_COMMIT] != 0.0) {
-      swap_current_candidate(h);
+      accept_candidate(h);
       t0 = now_s();
       if (int rc = launch_sweep(h, lm[LM_RADIUS])) return rc;
       if (int rc = read_sweep_scalars(h, &cost, &gmax, &bad)) return rc;
@@ -1348,7 +1412,7 @@ int lifcal_ba_reproj_stats(lifcal_ba_handle* h, double thr, lifcal_ba_stats* out
   Dev& d = h->d;
   HIP_TRY(hipSetDevice(h->opt.device));
   // reference :1028-1039: parameters are used as stored (no sign folding), scale goes through a float cast
-  if (int rc = launch_tables(h, d.cam, d.views, h->camc_stats, d.ft_c, d.lt_c, false, false)) return rc;
+  if (int rc = build_stats_tables(h)) return rc;
   HIP_TRY(hipMemsetAsync(h->stats_buf, 0, 8 * sizeof(double), h->stream));
   for (const TileSet* ts : {&h->ts1, &h->ts2}) {
     if (!ts->n_tiles) continue;
@@ -1392,7 +1456,7 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
   const size_t n = h->prob.n_obs;
   if (n == 0) return 0;
   HIP_TRY(hipSetDevice(h->opt.device));
-  if (int rc = launch_tables(h, d.cam, d.views, h->camc_stats, d.ft_c, d.lt_c, false, false)) return rc;
+  if (int rc = build_stats_tables(h)) return rc;
   uint32_t *src1 = nullptr, *src2 = nullptr; double* out = nullptr;
   auto release = [&]() { for (void* q : {(void*)src1, (void*)src2, (void*)out}) if (q) (void)hipFree(q); };
   auto up = [&](uint32_t** q, const std::vector<uint32_t>& v) -> hipError_t {
