@@ -333,6 +333,26 @@ int lifcal_ba_plan(const lifcal_ba_problem* p, int32_t rank, int32_t world_size,
                    uint32_t* obs_order /* [n_obs] or NULL: sorted position -> input index, UINT32_MAX-padded */,
                    uint32_t* point_owner /* [n_points] or NULL: rank owning each point */);
 
+/* The schedule of the LDS-window sweep that lifcal_ba_create builds for `rank` with default options in this environment (the same
+ * decision code: LIFCAL_SWEEP_KERNEL, LIFCAL_SWEEP_WAVES, LIFCAL_V2_BLOCKS, LIFCAL_GROUP_SPLIT, LIFCAL_DISABLE_V2, LIFCAL_PLAN_COST,
+ * LIFCAL_PLAN_BALANCE, and the fallback of LIFCAL_SWEEP_KERNEL=4 to k_sweep3 on frame windows too wide for k_back4), as the
+ * planner's cost model sees it.  options.deterministic / options.precision = 1 turn LIFCAL_SWEEP_KERNEL=4 into k_sweep3 at create;
+ * this entry point takes no options.  Host-only.  `violations` is recounted from the finished layout arrays, not taken from the
+ * planner's own bookkeeping: every regular point in exactly one pass, lanes and points of a pass within their caps, the lanes of a
+ * pass sorted by frame (frame-ordered kernels), lane sizes adding up to the observations, a point's and a pass's group ids each one
+ * contiguous run that no other point's groups share.  0 on a sound plan.  The block costs are those of the passes as built. */
+typedef struct lifcal_ba_plan_statistics {
+  uint32_t n_blocks, n_passes, pass_lanes, max_block_passes;
+  uint64_t n_lanes;            /* lanes over all passes ((point, frame) pairs after splitting)                                   */
+  uint64_t pass_steps;         /* sum over passes of the largest lane: observation steps the blocks walk                        */
+  uint64_t tile_steps;         /* sum over the 64-lane tiles of their largest lane: rows of the padded observation payload      */
+  uint64_t n_obs_window;       /* observations on the LDS-window path                                                           */
+  uint64_t n_points_permuted;  /* regular points whose processing position differs from their first-frame position              */
+  uint64_t violations;
+  double block_cost_mean, block_cost_max;   /* modelled cost of a block (C_STEP steps + C_PASS + C_LANE lanes, summed over its passes) */
+} lifcal_ba_plan_statistics;
+int lifcal_ba_plan_stats(const lifcal_ba_problem* p, int32_t rank, int32_t world_size, lifcal_ba_plan_statistics* out);
+
 /* ---- shard-local problems (multi-GPU without handing every rank the whole observation list) ----
  * lifcal_ba_create takes the WHOLE problem on every rank and keeps the observations of the points the rank owns.  For long
  * sequences (BASELINE configs[3], configs[4]) a launcher can instead partition ONCE from the index arrays alone (pt, fr: 8 bytes

@@ -122,6 +122,13 @@ class PlanInfo(C.Structure):
                 ("max_window_frames", C.c_uint32)]
 
 
+class PlanStats(C.Structure):     # lifcal_ba_plan_statistics
+    _fields_ = [("n_blocks", C.c_uint32), ("n_passes", C.c_uint32), ("pass_lanes", C.c_uint32), ("max_block_passes", C.c_uint32),
+                ("n_lanes", C.c_uint64), ("pass_steps", C.c_uint64), ("tile_steps", C.c_uint64), ("n_obs_window", C.c_uint64),
+                ("n_points_permuted", C.c_uint64), ("violations", C.c_uint64),
+                ("block_cost_mean", C.c_double), ("block_cost_max", C.c_double)]
+
+
 ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
@@ -286,6 +293,7 @@ PROTOTYPES = {
     "lifcal_ba_last_error": (C.c_char_p, []),
     "lifcal_ba_version": (C.c_char_p, []),
     "lifcal_ba_plan": (C.c_int, [C.POINTER(Problem), C.c_int32, C.c_int32, C.POINTER(PlanInfo), uptr, uptr]),
+    "lifcal_ba_plan_stats": (C.c_int, [C.POINTER(Problem), C.c_int32, C.c_int32, C.POINTER(PlanStats)]),
     "lifcal_ba_partition_points": (C.c_int, [C.POINTER(Problem), C.POINTER(Partition)]),
     "lifcal_ba_create_shard": (C.c_int, [C.POINTER(Problem), C.POINTER(Partition), C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "lifcal_ba_plan_shard": (C.c_int, [C.POINTER(Problem), C.POINTER(Partition), C.c_int32, C.POINTER(PlanInfo)]),

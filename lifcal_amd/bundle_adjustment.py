@@ -304,3 +304,12 @@ def plan(problem: capi.ProblemArrays, rank: int = 0, world_size: int = 1):
     owner = np.zeros(max(problem.struct.n_points, 1), np.uint32)
     _check(lib, lib.lifcal_ba_plan(C.byref(problem.struct), rank, world_size, C.byref(info), capi.as_uptr(order), capi.as_uptr(owner)), "lifcal_ba_plan")
     return info, order[: problem.struct.n_obs], owner[: problem.struct.n_points].astype(np.int32)
+
+
+def plan_stats(problem: capi.ProblemArrays, rank: int = 0, world_size: int = 1) -> capi.PlanStats:
+    """Host-only statistics of the LDS-window schedule create() would build in this environment (blocks, passes, lanes, observation
+    steps, modelled block cost, points moved by the processing order) and a count of layout violations recounted from the plan's arrays."""
+    lib = capi.load_library()
+    st = capi.PlanStats()
+    _check(lib, lib.lifcal_ba_plan_stats(C.byref(problem.struct), rank, world_size, C.byref(st)), "lifcal_ba_plan_stats")
+    return st

@@ -781,22 +781,75 @@ int lifcal_init_plenoptic_recalibration(double fL_fixed, double B_fixed, lifcal_
   return 0;
 }
 
+// The plan of a problem in this environment: kernel choice, lanes per pass, block count, group split and the fallbacks between the
+// sweep kernels, decided in ONE place for lifcal_ba_create, lifcal_ba_plan, lifcal_ba_plan_shard and lifcal_ba_plan_stats.
+//   LIFCAL_DISABLE_V2=1  every point through the global-atomic kernels
+//   LIFCAL_SWEEP_KERNEL, LIFCAL_SWEEP_WAVES  the window kernel and its waves per role (lanes per pass, lane order)
+//   LIFCAL_V2_BLOCKS     workgroups the LDS-window sweep is cut into (default: one per CU)
+//   LIFCAL_GROUP_SPLIT   observations per lane above which a (point, frame) group is cut into several lanes (0 = never; default:
+//                        chosen per block by the planner's cost model)
+struct PlanChoice { bool use_sweep3 = true, use_sweep4 = false; int sweep_waves = 4, b4_tpt = 1; };
+static int plan_for_environment(const lifcal_ba_problem* p, int rank, int world, int deterministic, int precision, const lifcal_ba_partition* part, Plan* pl, PlanChoice* c) {
+  const bool enable_v2 = getenv("LIFCAL_DISABLE_V2") == nullptr;
+  // the wave-specialised kernel wants the lanes of a pass sorted by frame, k_sweep2 (LIFCAL_SWEEP_KERNEL=2) by point
+  int kernel = sweep_kernel_from_env();
+  // ordered reductions and the fp32 evaluation exist in k_sweep3 only
+  if (kernel == 4 && (deterministic == 1 || precision == 1)) kernel = 3;
+  c->use_sweep3 = kernel != 2;   // (frame-ordered lanes: k_sweep3 and k_front4)
+  c->use_sweep4 = kernel == 4;
+  c->sweep_waves = sweep_waves_from_env(kernel == 3);
+  c->b4_tpt = 1;
+  if (deterministic == 1) {
+    if (!c->use_sweep3) { g_last_error = "options.deterministic = 1 needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; return LIFCAL_BA_ERR_INVALID_ARG; }
+    c->sweep_waves = 4;
+  }
+  if (precision == 1) {
+    // fp32 residual / Jacobian evaluation exists in the wave-specialised kernel with four waves per role only
+    if (!c->use_sweep3) { g_last_error = "options.precision = 1 needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; return LIFCAL_BA_ERR_INVALID_ARG; }
+    c->sweep_waves = 4;
+  }
+  uint32_t plan_lanes, plan_blocks; sweep_layout(kernel, c->sweep_waves, &plan_lanes, &plan_blocks);
+  const uint32_t v2_blocks = getenv("LIFCAL_V2_BLOCKS") ? (uint32_t)std::max(1, atoi(getenv("LIFCAL_V2_BLOCKS"))) : plan_blocks;
+  const uint32_t split_obs = getenv("LIFCAL_GROUP_SPLIT") ? (uint32_t)std::max(0, atoi(getenv("LIFCAL_GROUP_SPLIT"))) : UINT32_MAX;
+  if (int rc = build_plan(p, rank, world, pl, enable_v2, v2_blocks, split_obs, c->use_sweep3, plan_lanes, precision == 1, part)) return rc;
+  if (c->use_sweep4) {
+    // k_back4 keeps at most two 4x4 tiles of the window per thread of a 256-thread group: wider frame windows take k_sweep3
+    uint32_t max_ntri = 0;
+    for (uint32_t b = 0; b < pl->n_blocks; ++b) max_ntri = std::max(max_ntri, V4Back::ntri_of(pl->blk_nf[b], (uint32_t)pl->nc));
+    if (max_ntri > 512) {
+      c->use_sweep4 = false; c->sweep_waves = 4;
+      sweep_layout(3, 4, &plan_lanes, &plan_blocks);
+      *pl = Plan();
+      if (int rc = build_plan(p, rank, world, pl, enable_v2, getenv("LIFCAL_V2_BLOCKS") ? v2_blocks : plan_blocks, split_obs, true, plan_lanes, false, part)) return rc;
+    } else {
+      c->b4_tpt = max_ntri > 256 ? 2 : 1;
+    }
+  }
+  return 0;
+}
+
+static void fill_plan_info(const Plan& pl, lifcal_ba_plan_info* info) {
+  info->n_groups = pl.n_pairs; info->n_lenses = pl.n_lenses; info->n_promoted = pl.Q;
+  info->n_reduced = pl.n_red_canon; info->max_group_obs = pl.max_group_obs; info->n_chunks = pl.n_blocks; info->max_window_frames = pl.bw + 1;
+  info->n_tiles = pl.n_tiles + pl.pass_tiles() * pl.n_passes;
+}
+
 int lifcal_ba_plan(const lifcal_ba_problem* p, int32_t rank, int32_t world_size, lifcal_ba_plan_info* info,
                    uint32_t* obs_order, uint32_t* point_owner) {
-  Plan pl;
-  // the same layout lifcal_ba_create builds by default (lanes in frame order for the wave-specialised sweep kernel)
-  const int kernel = sweep_kernel_from_env();
-  const bool frame_order = kernel != 2;
-  const int waves = sweep_waves_from_env(kernel == 3);
-  uint32_t plan_lanes, plan_blocks; sweep_layout(kernel, waves, &plan_lanes, &plan_blocks);
-  if (int rc = build_plan(p, rank, world_size, &pl, true, plan_blocks, UINT32_MAX, frame_order, plan_lanes)) return rc;
-  if (info) {
-    info->n_groups = pl.n_pairs; info->n_tiles = pl.n_tiles; info->n_lenses = pl.n_lenses; info->n_promoted = pl.Q;
-    info->n_reduced = pl.n_red_canon; info->max_group_obs = pl.max_group_obs; info->n_chunks = pl.n_blocks; info->max_window_frames = pl.bw + 1;
-    info->n_tiles = pl.n_tiles + pl.pass_tiles() * pl.n_passes;
-  }
+  Plan pl; PlanChoice c;
+  // the layout lifcal_ba_create builds in this environment with default options
+  if (int rc = plan_for_environment(p, rank, world_size, 0, 0, nullptr, &pl, &c)) return rc;
+  if (info) fill_plan_info(pl, info);
   if (obs_order) { for (uint32_t i = 0; i < p->n_obs; ++i) obs_order[i] = UINT32_MAX; for (size_t s = 0; s < pl.obs_order.size(); ++s) obs_order[s] = pl.obs_order[s]; }
   if (point_owner) for (uint32_t q = 0; q < p->n_points; ++q) point_owner[q] = (uint32_t)pl.owner[q];
+  return 0;
+}
+
+int lifcal_ba_plan_stats(const lifcal_ba_problem* p, int32_t rank, int32_t world_size, lifcal_ba_plan_statistics* out) {
+  if (!out) return LIFCAL_BA_ERR_INVALID_ARG;
+  Plan pl; PlanChoice c;
+  if (int rc = plan_for_environment(p, rank, world_size, 0, 0, nullptr, &pl, &c)) return rc;
+  plan_stats(pl, out);
   return 0;
 }
 
@@ -813,16 +866,9 @@ int lifcal_ba_partition_points(const lifcal_ba_problem* index_only, lifcal_ba_pa
 
 int lifcal_ba_plan_shard(const lifcal_ba_problem* local, const lifcal_ba_partition* part, int32_t rank, lifcal_ba_plan_info* info) {
   if (!part || !info) return LIFCAL_BA_ERR_INVALID_ARG;
-  Plan pl;
-  const int kernel = sweep_kernel_from_env();
-  const bool frame_order = kernel != 2;
-  const int waves = sweep_waves_from_env(kernel == 3);
-  uint32_t plan_lanes, plan_blocks; sweep_layout(kernel, waves, &plan_lanes, &plan_blocks);
-  if (int rc = build_plan(local, rank, (int)part->world_size, &pl, true, plan_blocks, UINT32_MAX, frame_order, plan_lanes, false, part)) return rc;
-  info->n_groups = pl.n_pairs; info->n_lenses = pl.n_lenses; info->n_promoted = pl.Q;
-  info->n_reduced = pl.n_red_canon; info->max_group_obs = pl.max_group_obs; info->n_chunks = pl.n_blocks; info->max_window_frames = pl.bw + 1;
-  info->n_tiles = pl.n_tiles + pl.pass_tiles() * pl.n_passes;
-  if (getenv("LIFCAL_PLAN_HASH")) {}   // (build_plan prints the layout fingerprint itself)
+  Plan pl; PlanChoice c;
+  if (int rc = plan_for_environment(local, rank, (int)part->world_size, 0, 0, part, &pl, &c)) return rc;   // (build_plan prints the layout fingerprint itself)
+  fill_plan_info(pl, info);
   return 0;
 }
 
@@ -838,47 +884,14 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
   lifcal_ba_handle* h = new (std::nothrow) lifcal_ba_handle();
   if (!h) return LIFCAL_BA_ERR_NOMEM;
   h->opt = opt;
-  // tuning / A-B knobs (not part of the ABI): LIFCAL_DISABLE_V2=1 forces the global-atomic kernels,
-  // LIFCAL_V2_BLOCKS sets the number of workgroups the LDS-window sweep is cut into (default: one per CU)
-  const bool enable_v2 = getenv("LIFCAL_DISABLE_V2") == nullptr;
-  // the wave-specialised kernel wants the lanes of a pass sorted by frame, k_sweep2 (LIFCAL_SWEEP_KERNEL=2) by point
-  int kernel = sweep_kernel_from_env();
-  // ordered reductions and the fp32 evaluation exist in k_sweep3 only
-  if (kernel == 4 && (opt.deterministic == 1 || opt.precision == 1)) kernel = 3;
-  h->use_sweep3 = kernel != 2;   // (frame-ordered lanes: k_sweep3 and k_front4)
-  h->use_sweep4 = kernel == 4;
-  h->sweep_waves = sweep_waves_from_env(kernel == 3);
-  if (opt.deterministic == 1) {
-    if (!h->use_sweep3) { g_last_error = "options.deterministic = 1 needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; delete h; return LIFCAL_BA_ERR_INVALID_ARG; }
-    h->sweep_waves = 4;
-  }
-  if (opt.precision == 1) {
-    // fp32 residual / Jacobian evaluation exists in the wave-specialised kernel with four waves per role only
-    if (!h->use_sweep3) { g_last_error = "options.precision = 1 needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; delete h; return LIFCAL_BA_ERR_INVALID_ARG; }
-    h->sweep_waves = 4;
-  }
-  uint32_t plan_lanes, plan_blocks; sweep_layout(kernel, h->sweep_waves, &plan_lanes, &plan_blocks);
-  const uint32_t v2_blocks = getenv("LIFCAL_V2_BLOCKS") ? (uint32_t)std::max(1, atoi(getenv("LIFCAL_V2_BLOCKS"))) : plan_blocks;
-  // LIFCAL_GROUP_SPLIT: observations per lane above which a (point, frame) group is cut into several lanes
-  // (0 = never; default: chosen per block by the planner's cost model)
-  const uint32_t split_obs = getenv("LIFCAL_GROUP_SPLIT") ? (uint32_t)std::max(0, atoi(getenv("LIFCAL_GROUP_SPLIT"))) : UINT32_MAX;
   h->trace = getenv("LIFCAL_TRACE") != nullptr;
   PlanClock cclk;
-  int rc = build_plan(p, opt.rank, opt.world_size, &h->plan, enable_v2, v2_blocks, split_obs, h->use_sweep3, plan_lanes, opt.precision == 1, part);
-  if (rc) { delete h; return rc; }
-  if (h->use_sweep4) {
-    // k_back4 keeps at most two 4x4 tiles of the window per thread of a 256-thread group: wider frame windows take k_sweep3
-    uint32_t max_ntri = 0;
-    for (uint32_t b = 0; b < h->plan.n_blocks; ++b) max_ntri = std::max(max_ntri, V4Back::ntri_of(h->plan.blk_nf[b], (uint32_t)h->plan.nc));
-    if (max_ntri > 512) {
-      h->use_sweep4 = false; h->sweep_waves = 4;
-      sweep_layout(3, 4, &plan_lanes, &plan_blocks);
-      h->plan = Plan();
-      rc = build_plan(p, opt.rank, opt.world_size, &h->plan, enable_v2, getenv("LIFCAL_V2_BLOCKS") ? v2_blocks : plan_blocks, split_obs, true, plan_lanes, false, part);
-      if (rc) { delete h; return rc; }
-    } else {
-      h->b4_tpt = max_ntri > 256 ? 2 : 1;
-    }
+  {
+    // tuning / A-B knobs (not part of the ABI) and the kernel fallbacks: plan_for_environment
+    PlanChoice c;
+    const int rc = plan_for_environment(p, opt.rank, opt.world_size, opt.deterministic, opt.precision, part, &h->plan, &c);
+    if (rc) { delete h; return rc; }
+    h->use_sweep3 = c.use_sweep3; h->use_sweep4 = c.use_sweep4; h->sweep_waves = c.sweep_waves; h->b4_tpt = c.b4_tpt;
   }
   cclk.lap("create: plan");
   h->prob = *p;

@@ -12,6 +12,9 @@
 //     reference src/CameraModel.h:92-125 depends on the lens and the camera only);
 //   * points are ordered by the first frame that sees them; ranks own contiguous ranges of that
 //     order balanced by observation count;
+//   * inside a block of the LDS-window path the points are processed in order of falling mean observations per (point, frame)
+//     pair, so that lanes of like size share a pass; group ids follow that order, and the blocks are cut to even out the cost the
+//     planner's model gives them (LIFCAL_PLAN_BALANCE=0: point order, blocks by observation count);
 //   * points named as pointID_2 of a distance constraint (reference :916-925) are "promoted" into
 //     the reduced system so that the eliminated point blocks stay independent.
 // Pure host C++ (no HIP), so the CPU test-suite can exercise it through lifcal_ba_plan().
@@ -56,7 +59,6 @@ struct Plan {
   // config
   uint32_t config = 0;
   int n_radial = 0; bool tangential = false, refine_poses = false, robust = false, refine_points = false, adj = false;
-  int nc = 5;                       // live camera slots 5 + nRad + 2*tan
   bool use_poses = false, use_points = false, use_constraints = false;
   // point bookkeeping (global ids)
   std::vector<uint32_t> point_order;   // rank in the (first frame, id) order -> point id
@@ -92,6 +94,14 @@ struct Plan {
   uint32_t pass_tiles() const { return pass_lanes / 64; }
   uint32_t zd_doubles() const { return pass_lanes >= 256 ? ZD_DOUBLES : ZD_DOUBLES / 2; }
   uint32_t np_max() const { return pass_lanes == 64 ? 64u : pass_lanes / 4; }   // (64-lane passes: no Z matrix per pass, a tile may hold 64 one-lane points)
+  int nc = 5;                       // live camera slots 5 + nRad + 2*tan
+  // points a pass of a block with a window of nf frames may hold: the dense Z matrix of a pass (3 np rows x padded window columns) must
+  // fit its LDS budget (64-lane passes: k_front4 keeps no Z matrix per pass, k_back4 chunks the block's points itself)
+  uint32_t np_cap(uint32_t nf) const {
+    if (pass_lanes == 64) return np_max();
+    const uint32_t ncolp = ((6 * nf + (uint32_t)nc + 1) + 15u) & ~15u;
+    return std::max(1u, std::min<uint32_t>(np_max(), ((zd_doubles() / (ncolp + 2)) & ~7u) / 3));
+  }
   uint32_t n_blocks = 0, n_passes = 0, max_block_nf = 0;
   std::vector<uint8_t> pt_special;     // P: the point takes the v1 (global-atomic) kernels
   std::vector<uint32_t> rk_flo, rk_nfr;   // per rank: first frame and number of frames its points observe (identical on every rank)
@@ -110,6 +120,12 @@ struct Plan {
   ZeroVec<float> v2_du, v2_dv;         // options.precision = 1 only: (u - mcx, v - mcy) of the same rows in fp32
   std::vector<uint32_t> special_owned; // owned points handled by the v1 kernels (promoted / constrained / oversized)
   uint32_t n_obs_v2 = 0;
+  // the schedule of the v2 path as the planner's cost model sees it (lifcal_ba_plan_stats)
+  bool frame_order = false;            // lanes of a pass sorted by frame (k_sweep3, k_front4) or laid out by point (k_sweep2)
+  double c_step = 0.0, c_pass = 0.0, c_lane = 0.0;   // the cost model's constants: cycles per observation step of a pass, per pass, per lane
+  std::vector<double> blk_cost;        // per block: modelled cost of the passes as built, sum of c_step * largest lane + c_pass + c_lane * lanes
+                                       // (the per-pass dynamic program's optimum; more where a special point's groups cut a pass short, LIFCAL_PLAN_BALANCE=0)
+  uint32_t n_permuted = 0;             // regular points whose processing position differs from their first-frame position
   // lenses
   std::vector<double> lens_xy;         // 2 per lens
   uint32_t n_lenses = 0;
@@ -485,9 +501,10 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
   for (const Group& G : groups) if (G.n > 255) special[G.pt] = 1;   // the v2 slot word keeps the group size in 8 bits
 
   clk.lap("classify");
-  // --- v2 blocks: contiguous ranges of regular points with ~reg_obs/target observations each, window <= NF_MAX ---
+  // --- v2 blocks: contiguous ranges of regular points with ~reg_obs/target observations each, window <= NF_MAX (the start of the
+  // cost-balanced cut below, and the cut itself under LIFCAL_PLAN_BALANCE=0) ---
   std::vector<uint32_t> reg;                 // regular points in point order
-  std::vector<size_t> blk_begin;             // block b = reg[blk_begin[b] .. blk_begin[b+1])
+  std::vector<size_t> blk_begin;             // block b = reg[blk_begin[b] .. blk_begin[b+1]): the same positions in `proc` once the order is chosen
   L.blk_flo.clear(); L.blk_nf.clear(); L.max_block_nf = 0;
   L.n_obs_v2 = 0;
   {
@@ -511,12 +528,8 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
     }
     blk_begin.push_back(reg.size());
   }
-  auto block_np_cap = [&](size_t b) {
-    if (PL == 64) return L.np_max();   // k_front4 keeps no Z matrix per pass (k_back4 chunks the block's points itself)
-    // the dense Z matrix of a pass (3 np rows x padded window columns) must fit its LDS budget
-    const uint32_t ncolp = ((6 * L.blk_nf[b] + (uint32_t)L.nc + 1) + 15u) & ~15u;
-    return std::max(1u, std::min<uint32_t>(L.np_max(), ((L.zd_doubles() / (ncolp + 2)) & ~7u) / 3));
-  };
+  auto np_cap_of = [&](uint32_t nf) { return L.np_cap(nf); };
+  auto block_np_cap = [&](size_t b) { return np_cap_of(L.blk_nf[b]); };
 
   clk.lap("v2 blocks");
   // --- lanes: a (point, frame) group of a regular point with more than T observations is cut into near-equal parts, one
@@ -526,6 +539,10 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
   // over a cost model of k_sweep2 (cycles measured with the in-kernel stamps at the 1 M-observation point).
   L.n_pairs = L.n_groups;
   std::vector<uint8_t> pass_break(L.P, 0);   // a pass of the plan below starts at this point
+  std::vector<uint32_t> proc;                // regular points in processing order: block b = proc[blk_begin[b] .. blk_begin[b+1])
+  // LIFCAL_PLAN_BALANCE=0: points processed in point order, blocks cut by observation count (A/B arm of the two steps below)
+  const bool balance = !(getenv("LIFCAL_PLAN_BALANCE") && atoi(getenv("LIFCAL_PLAN_BALANCE")) == 0);
+  L.frame_order = frame_order;
   {
     std::vector<uint32_t> split_of(L.P, 0);   // 0 = leave the point's groups whole
     auto parts_of = [](uint32_t n, uint32_t T) { return T ? (n + T - 1) / T : 1u; };
@@ -533,50 +550,145 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
     // (64-lane passes, k_front4: a tile costs its observation steps plus the emission / gather of one wave; lanes are nearly free)
     double C_STEP = PL == 64 ? 1000.0 : 4700.0, C_PASS = (PL >= 256 ? 21500.0 : (PL == 128 ? 13000.0 : 3000.0)), C_LANE = PL == 64 ? 10.0 : 65.0;
     if (const char* e = getenv("LIFCAL_PLAN_COST")) { double a, b2, c2; if (sscanf(e, "%lf,%lf,%lf", &a, &b2, &c2) == 3) { C_STEP = a; C_PASS = b2; C_LANE = c2; } }
-    // blocks are independent (each writes split_of / pass_break of its own points only)
-    plan_parallel_for(blk_begin.empty() ? 0u : (uint32_t)(blk_begin.size() - 1), 4, [&](uint32_t b) {
-      const uint32_t np_cap = block_np_cap(b);
-      const size_t i0 = blk_begin[b], n = blk_begin[b + 1] - i0;
-      uint32_t nmax = 0;
-      for (size_t k = 0; k < n; ++k)
-        for (uint32_t g = L.pt_slot0[reg[i0 + k]]; g < L.pt_slot0[reg[i0 + k]] + L.pt_nslots[reg[i0 + k]]; ++g) nmax = std::max(nmax, groups[g].n);
-      // candidate split sizes: 0 (whole groups) and, in automatic mode, 2 .. min(largest group, 16); a fixed request otherwise
-      std::vector<uint32_t> Ts(1, 0u);
-      if (split_obs == UINT32_MAX) { for (uint32_t T = 2; T <= std::min(nmax, 16u); ++T) Ts.push_back(T); }
-      else if (split_obs > 0) Ts.assign(1, split_obs);
-      const size_t nT = Ts.size();
-      std::vector<uint32_t> lanes(n * nT), steps(n * nT);
-      for (size_t k = 0; k < n; ++k)
-        for (size_t t = 0; t < nT; ++t) {
-          uint32_t l = 0, st = 0;
-          for (uint32_t g = L.pt_slot0[reg[i0 + k]]; g < L.pt_slot0[reg[i0 + k]] + L.pt_nslots[reg[i0 + k]]; ++g) {
-            const uint32_t parts = parts_of(groups[g].n, Ts[t]);
-            l += parts; st = std::max(st, (groups[g].n + parts - 1) / parts);
-          }
-          lanes[k * nT + t] = l; steps[k * nT + t] = st;
+    L.c_step = C_STEP; L.c_pass = C_PASS; L.c_lane = C_LANE;
+    // candidate split sizes: 0 (whole groups) and, in automatic mode, 2 .. 16, of which a block tries those up to its largest group;
+    // a fixed request otherwise
+    std::vector<uint32_t> Ts(1, 0u);
+    if (split_obs == UINT32_MAX) { for (uint32_t T = 2; T <= 16u; ++T) Ts.push_back(T); }
+    else if (split_obs > 0) Ts.assign(1, split_obs);
+    const size_t nT = Ts.size(), R = reg.size();
+    // per regular point: lanes and observation steps at every split size, largest group, observations, (point, frame) pairs.
+    // Computed once: the block cut below runs the dynamic program on several ranges of the same points.
+    std::vector<uint32_t> lanes(R * nT), steps(R * nT), gmax(R), robs(R), rpairs(R);
+    plan_parallel_for((uint32_t)R, 256, [&](uint32_t i) {
+      const uint32_t q = reg[i], ga = L.pt_slot0[q], gb = ga + L.pt_nslots[q];
+      uint32_t m = 0, o = 0;
+      for (uint32_t g = ga; g < gb; ++g) { m = std::max(m, groups[g].n); o += groups[g].n; }
+      gmax[i] = m; robs[i] = o; rpairs[i] = gb - ga;
+      for (size_t t = 0; t < nT; ++t) {
+        uint32_t l = 0, st = 0;
+        if (Ts[t] == 0 || Ts[t] >= m) { l = gb - ga; st = m; }   // no group of the point is cut at this size
+        else for (uint32_t g = ga; g < gb; ++g) {
+          const uint32_t n = groups[g].n;
+          if (n <= Ts[t]) { l += 1; st = std::max(st, n); continue; }
+          const uint32_t parts = parts_of(n, Ts[t]);
+          l += parts; st = std::max(st, (n + parts - 1) / parts);
         }
+        lanes[i * nT + t] = l; steps[i * nT + t] = st;
+      }
+    });
+    // One block: its points reg[i0 .. i1) in processing order, and the dynamic program over them.  A pass costs its LARGEST lane
+    // (every wave walks max(lane size) steps and the tiles meet at a barrier), so the points are processed in order of falling mean
+    // observations per (point, frame) pair, ties in point order: lanes of like size share a pass.  LIFCAL_PLAN_BALANCE=0 keeps the
+    // point order.
+    struct BlockPlan { size_t i0 = 0, i1 = 0; uint32_t flo = 0, nf = 0; double cost = 0.0; std::vector<uint32_t> ord, pick, nxt; };
+    auto solve_block = [&](BlockPlan& B) {
+      const size_t n = B.i1 - B.i0;
+      const uint32_t np_cap = np_cap_of(B.nf);
+      B.ord.resize(n);
+      std::iota(B.ord.begin(), B.ord.end(), (uint32_t)B.i0);
+      if (balance)
+        std::sort(B.ord.begin(), B.ord.end(), [&](uint32_t a, uint32_t b) {
+          const uint64_t x = (uint64_t)robs[a] * rpairs[b], y = (uint64_t)robs[b] * rpairs[a];
+          return x != y ? x > y : a < b;
+        });
+      uint32_t nmax = 0;
+      for (size_t i = B.i0; i < B.i1; ++i) nmax = std::max(nmax, gmax[i]);
+      const size_t nTb = (split_obs == UINT32_MAX && nmax >= 2) ? (size_t)std::min(nmax, 16u) : 1;   // the first nTb entries of Ts
+      std::vector<uint32_t> bl(n * nTb), bs(n * nTb);
+      for (size_t k = 0; k < n; ++k)
+        for (size_t t = 0; t < nTb; ++t) { bl[k * nTb + t] = lanes[(size_t)B.ord[k] * nT + t]; bs[k * nTb + t] = steps[(size_t)B.ord[k] * nT + t]; }
       // dynamic program over the block's points: a pass = maximal run of points that fits 256 lanes / np_cap points at ONE
       // split size; cost[i] = cheapest way to cover points i.. (more lanes can mean one more pass, fewer steps per pass)
       std::vector<double> cost(n + 1, 0.0);
-      std::vector<uint32_t> pick(n, 0), nxt(n, 0);
+      B.pick.assign(n, 0); B.nxt.assign(n, 0);
       for (size_t i = n; i-- > 0;) {
         double best = 1e300;
-        for (size_t t = 0; t < nT; ++t) {
+        for (size_t t = 0; t < nTb; ++t) {
           uint32_t ng = 0, st = 0; size_t e = i;
-          while (e < n && e - i < np_cap && ng + lanes[e * nT + t] <= PL) { ng += lanes[e * nT + t]; st = std::max(st, steps[e * nT + t]); ++e; }
+          while (e < n && e - i < np_cap && ng + bl[e * nTb + t] <= PL) { ng += bl[e * nTb + t]; st = std::max(st, bs[e * nTb + t]); ++e; }
           if (e == i) continue;                                                  // a single point too wide for this split size
-          if (Ts[t] != 0 && lanes[i * nT + t] > (PL == 64 ? PL / 2 : PL / 4) && nT > 1) continue;   // keep several points per pass
+          if (Ts[t] != 0 && bl[i * nTb + t] > (PL == 64 ? PL / 2 : PL / 4) && nTb > 1) continue;   // keep several points per pass
           const double c = C_STEP * st + C_PASS + C_LANE * ng + cost[e];
-          if (c < best) { best = c; pick[i] = (uint32_t)t; nxt[i] = (uint32_t)e; }
+          if (c < best) { best = c; B.pick[i] = (uint32_t)t; B.nxt[i] = (uint32_t)e; }
         }
-        if (best == 1e300) { pick[i] = 0; nxt[i] = (uint32_t)i + 1; best = C_PASS + cost[i + 1]; }   // whole groups always fit (regular points have <= 256 groups)
+        if (best == 1e300) { B.pick[i] = 0; B.nxt[i] = (uint32_t)i + 1; best = C_PASS + cost[i + 1]; }   // whole groups always fit (regular points have <= 256 groups)
         cost[i] = best;
       }
-      for (size_t i = 0; i < n; i = nxt[i]) {
-        for (size_t k = i; k < nxt[i]; ++k) split_of[reg[i0 + k]] = Ts[pick[i]];
-        if (i > 0) pass_break[reg[i0 + i]] = 1;
+      B.cost = cost[0];
+    };
+    const uint32_t nb0 = blk_begin.empty() ? 0u : (uint32_t)(blk_begin.size() - 1);
+    std::vector<BlockPlan> blocks(nb0);
+    for (uint32_t b = 0; b < nb0; ++b) { blocks[b].i0 = blk_begin[b]; blocks[b].i1 = blk_begin[b + 1]; blocks[b].flo = L.blk_flo[b]; blocks[b].nf = L.blk_nf[b]; }
+    plan_parallel_for(nb0, 4, [&](uint32_t b) { solve_block(blocks[b]); });
+    if (balance && nb0 > 1) {
+      // The sweep launches one workgroup per block and ends with the slowest one, so the blocks are re-cut to even out their MODELLED
+      // cost (the cut by observation count above is the start and the fallback): every point takes the share of its block's cost that
+      // its observations have, the points are cut into ranges of equal weight, the new blocks are solved, and so on for a few rounds.
+      // The cut with the smallest largest block wins; a cut that needs more blocks than the start is dropped.  The weights are sums
+      // of per-block results, so the outcome does not depend on how many threads solved the blocks.
+      const int rounds = 4;   // (bench scene: the largest block settles within 0.2 % after the third)
+      auto max_cost = [](const std::vector<BlockPlan>& v) { double m = 0.0; for (const BlockPlan& B : v) m = std::max(m, B.cost); return m; };
+      std::vector<BlockPlan> cur = blocks;
+      double best = max_cost(blocks);
+      std::vector<double> w(R);
+      for (int round = 0; round < rounds; ++round) {
+        double remaining = 0.0;
+        for (const BlockPlan& B : cur) {
+          uint64_t o = 0;
+          for (size_t i = B.i0; i < B.i1; ++i) o += robs[i];
+          for (size_t i = B.i0; i < B.i1; ++i) w[i] = B.cost * (double)robs[i] / (double)o;
+          remaining += B.cost;
+        }
+        std::vector<BlockPlan> next;
+        bool fits = true;
+        for (size_t i = 0; i < R;) {
+          if (next.size() == nb0) { fits = false; break; }
+          const size_t left = nb0 - next.size();
+          const double target = remaining / (double)left;
+          uint32_t flo = UINT32_MAX, fhi = 0; double acc = 0.0; size_t j = i;
+          while (j < R) {
+            const uint32_t q = reg[j];
+            const uint32_t nlo = std::min(flo, first[q]), nhi = std::max(fhi, last[q]);
+            if (j > i && (nhi - nlo + 1 > Plan::NF_MAX || (left > 1 && acc + 0.5 * w[j] > target))) break;
+            flo = nlo; fhi = nhi; acc += w[j]; ++j;
+          }
+          BlockPlan B; B.i0 = i; B.i1 = j; B.flo = flo; B.nf = fhi - flo + 1;
+          next.push_back(std::move(B));
+          remaining -= acc; i = j;
+        }
+        if (!fits) break;
+        // a block whose range did not change keeps its solution
+        std::vector<uint32_t> todo;
+        for (size_t b = 0, c = 0; b < next.size(); ++b) {
+          while (c < cur.size() && cur[c].i0 < next[b].i0) ++c;
+          if (c < cur.size() && cur[c].i0 == next[b].i0 && cur[c].i1 == next[b].i1) next[b] = cur[c];
+          else todo.push_back((uint32_t)b);
+        }
+        if (todo.empty()) break;   // the cut has settled
+        plan_parallel_for((uint32_t)todo.size(), 4, [&](uint32_t k) { solve_block(next[todo[k]]); });
+        const double m = max_cost(next);
+        if (m < best) { best = m; blocks = next; }
+        cur.swap(next);
       }
-    });
+    }
+    // the chosen cut: block ranges, processing order, split size and pass starts of every point
+    blk_begin.clear(); L.blk_flo.clear(); L.blk_nf.clear(); L.max_block_nf = 0;
+    proc.clear(); proc.reserve(R);
+    for (const BlockPlan& B : blocks) {
+      blk_begin.push_back(B.i0);
+      L.blk_flo.push_back(B.flo); L.blk_nf.push_back(B.nf);
+      L.max_block_nf = std::max(L.max_block_nf, B.nf);
+      const size_t n = B.i1 - B.i0;
+      for (size_t k = 0; k < n; ++k) proc.push_back(reg[B.ord[k]]);
+      for (size_t i = 0; i < n; i = B.nxt[i]) {
+        for (size_t k = i; k < B.nxt[i]; ++k) split_of[reg[B.ord[k]]] = Ts[B.pick[i]];
+        if (i > 0) pass_break[reg[B.ord[i]]] = 1;
+      }
+    }
+    blk_begin.push_back(R);
+    L.n_permuted = 0;
+    for (size_t k = 0; k < R; ++k) L.n_permuted += proc[k] != reg[k] ? 1u : 0u;
     std::vector<Group> cut;
     cut.reserve(groups.size() * 2);
     for (const Group& G : groups) {
@@ -587,6 +699,18 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
         cut.push_back({G.pt, G.fr, s0, n});
         s0 += n;
       }
+    }
+    if (balance) {
+      // group ids follow the processing order: the regular points' groups block by block in the order the passes take them, then
+      // the special points' groups in point order.  A point's groups stay one run of gids, a pass's groups are one run, and no
+      // special point's groups sit inside a pass's run.
+      std::vector<uint32_t> g0(L.P, 0), gn(L.P, 0);
+      for (uint32_t g = 0; g < (uint32_t)cut.size(); ++g) { if (gn[cut[g].pt] == 0) g0[cut[g].pt] = g; gn[cut[g].pt]++; }
+      std::vector<Group> byproc;
+      byproc.reserve(cut.size());
+      for (uint32_t q : proc) for (uint32_t g = g0[q]; g < g0[q] + gn[q]; ++g) byproc.push_back(cut[g]);
+      for (const Group& G : cut) if (special[G.pt]) byproc.push_back(G);
+      cut.swap(byproc);
     }
     groups.swap(cut);
     L.n_groups = (uint32_t)groups.size();
@@ -639,11 +763,11 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
     while (a < j) {
       uint32_t ng = 0, np = 0; size_t e = a;
       // a pass covers one contiguous run of gids (a special point's groups in between end the pass)
-      while (e < j && np < np_cap && ng + L.pt_nslots[reg[e]] <= PL && !(e > a && pass_break[reg[e]]) &&
-             (e == a || L.pt_slot0[reg[e]] == L.pt_slot0[reg[e - 1]] + L.pt_nslots[reg[e - 1]])) { ng += L.pt_nslots[reg[e]]; ++np; ++e; }
+      while (e < j && np < np_cap && ng + L.pt_nslots[proc[e]] <= PL && !(e > a && pass_break[proc[e]]) &&
+             (e == a || L.pt_slot0[proc[e]] == L.pt_slot0[proc[e - 1]] + L.pt_nslots[proc[e - 1]])) { ng += L.pt_nslots[proc[e]]; ++np; ++e; }
       L.pass_pt0.push_back((uint32_t)L.v2_points.size()); L.pass_np.push_back(np);
-      L.pass_gid0.push_back(L.pt_slot0[reg[a]]); L.pass_ng.push_back(ng);
-      { uint32_t g0 = 0; for (size_t k = a; k < e; ++k) { L.v2_points.push_back(reg[k]); L.v2_ptinfo.push_back(g0 | (L.pt_nslots[reg[k]] << 16)); g0 += L.pt_nslots[reg[k]]; } }
+      L.pass_gid0.push_back(L.pt_slot0[proc[a]]); L.pass_ng.push_back(ng);
+      { uint32_t g0 = 0; for (size_t k = a; k < e; ++k) { L.v2_points.push_back(proc[k]); L.v2_ptinfo.push_back(g0 | (L.pt_nslots[proc[k]] << 16)); g0 += L.pt_nslots[proc[k]]; } }
       a = e;
     }
     L.blk_pass0.push_back((uint32_t)L.pass_pt0.size());
@@ -731,6 +855,15 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
     });
   }
 
+  // modelled cost of the blocks from the passes as they were built
+  L.blk_cost.assign(L.n_blocks, 0.0);
+  for (uint32_t b = 0; b < L.n_blocks; ++b)
+    for (uint32_t ps = L.blk_pass0[b]; ps < L.blk_pass0[b + 1]; ++ps) {
+      uint32_t st = 0;
+      for (uint32_t w = 0; w < PT; ++w) st = std::max(st, L.v2_tile_row0[(size_t)ps * PT + w + 1] - L.v2_tile_row0[(size_t)ps * PT + w]);
+      L.blk_cost[b] += L.c_step * st + L.c_pass + L.c_lane * L.pass_ng[ps];
+    }
+
   clk.lap("v2 passes");
   // --- constraints owned by this rank; CSR of partner columns per eliminated point ---
   L.my_constraints.clear();
@@ -764,6 +897,86 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
     std::fprintf(stderr, "[plan] hash %016llx\n", (unsigned long long)h);
   }
   return 0;
+}
+
+// Statistics of the v2 schedule of a finished plan (lifcal_ba_plan_stats).  `violations` is recounted from the arrays the kernels
+// read (passes, slots, group ids), not from the planner's dynamic program.
+inline void plan_stats(const Plan& L, lifcal_ba_plan_statistics* out) {
+  lifcal_ba_plan_statistics s;
+  std::memset(&s, 0, sizeof(s));
+  const uint32_t PL = L.pass_lanes, PT = L.pass_tiles();
+  s.n_blocks = L.n_blocks; s.n_passes = L.n_passes; s.pass_lanes = PL;
+  s.n_obs_window = L.n_obs_v2; s.n_points_permuted = L.n_permuted;
+  for (uint32_t b = 0; b < L.n_blocks; ++b) s.max_block_passes = std::max(s.max_block_passes, L.blk_pass0[b + 1] - L.blk_pass0[b]);
+  for (uint32_t ps = 0; ps < L.n_passes; ++ps) {
+    s.n_lanes += L.pass_ng[ps];
+    uint32_t m = 0;
+    for (uint32_t w = 0; w < PT; ++w) { const uint32_t r = L.v2_tile_row0[(size_t)ps * PT + w + 1] - L.v2_tile_row0[(size_t)ps * PT + w]; s.tile_steps += r; m = std::max(m, r); }
+    s.pass_steps += m;
+  }
+  for (double c : L.blk_cost) { s.block_cost_mean += c; s.block_cost_max = std::max(s.block_cost_max, c); }
+  if (!L.blk_cost.empty()) s.block_cost_mean /= (double)L.blk_cost.size();
+
+  uint64_t bad = 0;
+  // who owns each group id: every gid belongs to exactly one point (a point's groups are one run, runs do not overlap)
+  std::vector<uint32_t> gid_pt(L.n_groups, UINT32_MAX);
+  for (uint32_t q = 0; q < L.P; ++q) {
+    if (L.pt_nslots[q] == 0) continue;
+    if ((uint64_t)L.pt_slot0[q] + L.pt_nslots[q] > L.n_groups) { ++bad; continue; }
+    for (uint32_t g = L.pt_slot0[q]; g < L.pt_slot0[q] + L.pt_nslots[q]; ++g) { if (gid_pt[g] != UINT32_MAX) ++bad; gid_pt[g] = q; }
+  }
+  for (uint32_t g = 0; g < L.n_groups; ++g) if (gid_pt[g] == UINT32_MAX) ++bad;
+  std::vector<uint32_t> in_pass(L.P, 0);
+  std::vector<uint8_t> seen;
+  uint64_t lane_obs = 0;
+  if (L.blk_pass0.size() != (size_t)L.n_blocks + 1 || (L.n_blocks && L.blk_pass0[L.n_blocks] != L.n_passes)) ++bad;
+  else for (uint32_t b = 0; b < L.n_blocks; ++b) {
+    const uint32_t np_cap = L.np_cap(L.blk_nf[b]);
+    for (uint32_t ps = L.blk_pass0[b]; ps < L.blk_pass0[b + 1]; ++ps) {
+      const uint32_t np = L.pass_np[ps], ng = L.pass_ng[ps], gid0 = L.pass_gid0[ps];
+      if (ng > PL || np > np_cap || np == 0 || (uint64_t)gid0 + ng > L.n_groups) { ++bad; continue; }
+      // the pass's points: regular, their gid runs chained from pass_gid0, the descriptors consistent
+      uint32_t g = gid0;
+      for (uint32_t k = 0; k < np; ++k) {
+        const uint32_t q = L.v2_points[L.pass_pt0[ps] + k];
+        if (q >= L.P) { ++bad; continue; }
+        in_pass[q]++;
+        if (L.pt_special[q] || L.pt_slot0[q] != g) ++bad;
+        if (L.v2_ptinfo[L.pass_pt0[ps] + k] != ((g - gid0) | (L.pt_nslots[q] << 16)) || L.v2_passpt[(size_t)ps * Plan::NP_MAX + k] != q) ++bad;
+        g += L.pt_nslots[q];
+      }
+      if (g != gid0 + ng) ++bad;
+      // the pass's lanes: each gid of the run exactly once, frame and point of the lane those of its gid, inside the block's window
+      seen.assign(ng, 0);
+      uint32_t lanes = 0, prev_fr = 0;
+      for (uint32_t k = 0; k < PL; ++k) {
+        // k-th lane of the pass: tile k / 64 in frame order, tile k % PT otherwise (the slot order of build_plan)
+        const size_t at = (size_t)ps * PL + (L.frame_order ? k : (k % PT) * 64 + k / PT);
+        const uint32_t n = L.v2f_cnt[at];
+        if (n == 0) { if (L.v2_slot[at] != 0) ++bad; continue; }
+        if (lanes != k) ++bad;   // lanes are packed: no idle slot before a live one
+        ++lanes; lane_obs += n;
+        const uint32_t gi = L.v2_gidx[at], fr = L.v2f_fr[at];
+        if (gi < gid0 || gi >= gid0 + ng) { ++bad; continue; }
+        if (seen[gi - gid0]) ++bad;
+        seen[gi - gid0] = 1;
+        if (gid_pt[gi] != L.v2f_pt[at] || L.gid_fr[gi] != fr || fr < L.blk_flo[b] || fr - L.blk_flo[b] >= L.blk_nf[b]) ++bad;
+        if (L.frame_order && lanes > 1 && fr < prev_fr) ++bad;
+        prev_fr = fr;
+      }
+      if (lanes != ng) ++bad;
+    }
+  }
+  // every regular point of this rank in exactly one pass, nobody else in any
+  std::vector<uint8_t> owned(L.P, 0);
+  for (uint32_t q : L.owned_points) owned[q] = 1;
+  for (uint32_t q = 0; q < L.P; ++q) {
+    const bool regular = owned[q] && !L.pt_special[q] && L.pt_nslots[q] > 0;
+    if (in_pass[q] != (regular ? 1u : 0u)) ++bad;
+  }
+  if (lane_obs != L.n_obs_v2) ++bad;
+  s.violations = bad;
+  *out = s;
 }
 
 // the ownership rule of build_plan applied to the index arrays of the whole problem (lifcal_ba_partition_points)

@@ -19,3 +19,5 @@ for _ in range(3):
     t = time.time()
     info, order, owner = lifcal_amd.plan(pa)
     print("plan seconds", round(time.time() - t, 4))
+st = lifcal_amd.plan_stats(pa)
+print("plan stats", {f: getattr(st, f) for f, _ in st._fields_})
