@@ -276,6 +276,43 @@ typedef struct lifcal_ba_object_space {
 int lifcal_ba_object_space_stats(lifcal_ba_handle* h, uint64_t n, const double* x, const double* y, const double* vdepth, const uint32_t* fr,
                                  const uint32_t* pt, double* ref_c, double* proj_c, lifcal_ba_object_space* out);
 
+/* ---- residual report: the reprojection errors grouped by frame, point and micro lens ----
+ * Evaluated at the device-resident parameters exactly as lifcal_ba_reproj_stats evaluates them (parameters as stored, no sign
+ * folding).  e = projected - observed in raw pixels.  Every table is a segmented sum in a fixed order (no atomics): the output is
+ * bitwise reproducible whatever options.deterministic says.  A lens id is the planner's de-duplicated lens index (exact-bit equal
+ * (mcx, mcy) share one id); it is stable for the handle and lens_xy[2 id], lens_xy[2 id + 1] are the (mcx, mcy) of its observations.
+ * One rank (world_size > 1: LIFCAL_BA_ERR_INVALID_ARG); every arity, options.precision 0 and 1.  The handle is left as it was. */
+typedef struct lifcal_ba_group_stats {      /* 64 bytes, one row per group; an empty group is all zeros */
+  double sum_x, sum_y;        /* sum of e_x, e_y -> mean offset                                                         */
+  double sum_xx, sum_yy;      /* sum of e_x^2, e_y^2 -> RMS as calcReprojectionError defines it                         */
+  double sum_w;               /* sum of the loss weight rho'(|e|^2); equals n when the loss is off                      */
+  double max_abs_x, max_abs_y;
+  uint32_t n, n_inliers;      /* |e|^2 <= thr^2, the reference's rule (:1088)                                           */
+} lifcal_ba_group_stats;
+
+/* (the structure carries the suffix _io: in C a typedef and a function cannot share the name lifcal_ba_residual_report) */
+typedef struct lifcal_ba_residual_report_io {
+  double inlier_threshold;             /* in */
+  double* ex; double* ey;              /* [n_obs] or NULL, caller's observation order                                   */
+  double* weight;                      /* [n_obs] or NULL: 1 / (1 + |e|^2 / loss_scale^2) if the config has the robust bit, else 1 */
+  uint32_t* lens;                      /* [n_obs] or NULL: lens id of the observation, < n_lenses                        */
+  double* lens_xy;                     /* [2 * n_lenses] or NULL: centre of lens id k                                    */
+  lifcal_ba_group_stats* per_frame;    /* [n_frames] or NULL */
+  lifcal_ba_group_stats* per_point;    /* [n_points] or NULL */
+  lifcal_ba_group_stats* per_lens;     /* [n_lenses] or NULL (n_lenses: lifcal_ba_get_info)                              */
+  lifcal_ba_group_stats total;         /* out */
+  double seconds;                      /* out: device time of the call */
+} lifcal_ba_residual_report_io;
+int lifcal_ba_residual_report(lifcal_ba_handle* h, lifcal_ba_residual_report_io* io);
+
+/* the same statistics for any grouping the caller chooses (sensor cells, depth bins, ...): key[i] < n_keys for every observation,
+ * caller's order; out[n_keys].  The keys are checked on the host before anything is launched (LIFCAL_BA_ERR_INVALID_ARG). */
+int lifcal_ba_residual_groups(lifcal_ba_handle* h, double inlier_threshold, uint32_t n_keys, const uint32_t* key, lifcal_ba_group_stats* out);
+
+/* Host-only: the index the grouped sums walk, a stable counting sort.  off[n_keys + 1], idx[n]: idx[off[k] .. off[k + 1]) are the
+ * positions i with key[i] == k, ascending.  LIFCAL_BA_ERR_INVALID_ARG for a key >= n_keys (or a null pointer). */
+int lifcal_group_index(uint32_t n, uint32_t n_keys, const uint32_t* key, uint32_t* off, uint32_t* idx);
+
 /* Poses held constant: fixed[f] != 0 keeps views[6f..6f+5] at their stored values in every following sweep / solve (ceres
  * SetParameterBlockConstant on that pose block: the frame's observations still constrain camera and points, its six columns
  * leave the reduced system).  fixed == NULL frees all poses again.  No reference counterpart; it is what the frame-windowed

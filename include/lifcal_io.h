@@ -15,6 +15,7 @@
 #ifndef LIFCAL_IO_H
 #define LIFCAL_IO_H
 #include <stdint.h>
+#include "lifcal_ba.h"   /* lifcal_ba_group_stats */
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -60,6 +61,13 @@ int lifcal_write_camera_orientations_ply(const char* path, uint32_t n_frames, co
 /* <dir>/cameraCoordinates_%04d.ply of one frame (:1244-1286), frame_id = frame.id: serves refCameraCoordinates/ (ref_c of
  * lifcal_ba_object_space_stats) and projectedCameraCoordinates/ (proj_c); xyz: [3 n_points] of the frame.  The directory must exist. */
 int lifcal_write_camera_coordinates_ply(const char* dir, int32_t frame_id, uint64_t n_points, const double* xyz);
+
+/* One table of lifcal_ba_residual_report (or of lifcal_ba_residual_groups) as CSV; no reference counterpart.  A header line, then one
+ * line per NON-EMPTY group k < n: "id[,x,y],n,n_inliers,mean_x,mean_y,rms_x,rms_y,max_abs_x,max_abs_y,mean_weight", floats as %.6f.
+ * id = ids[k], or k when ids is NULL (id_header names the column: "frame", "point", "lens", ...); the x,y columns are xy[2k], xy[2k + 1]
+ * (the lens centres of the per-lens table) and are left out when xy is NULL. */
+int lifcal_write_group_stats_csv(const char* path, const char* id_header, uint64_t n, const int32_t* ids, const double* xy,
+                                 const lifcal_ba_group_stats* rows);
 
 #ifdef __cplusplus
 }

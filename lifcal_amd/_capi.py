@@ -210,6 +210,7 @@ IO_PROTOTYPES = {
     "lifcal_write_object_coordinates_colmap_ids": (C.c_int, [C.c_char_p, C.c_uint64, _iptr, dptr]),
     "lifcal_write_camera_orientations_ply": (C.c_int, [C.c_char_p, C.c_uint32, dptr, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double, C.c_double]),
     "lifcal_write_camera_coordinates_ply": (C.c_int, [C.c_char_p, C.c_int32, C.c_uint64, dptr]),
+    "lifcal_write_group_stats_csv": (C.c_int, [C.c_char_p, C.c_char_p, C.c_uint64, _iptr, dptr, C.c_void_p]),
 }
 
 class ColmapInfo(C.Structure):     # include/lifcal_colmap.h lifcal_colmap_info
@@ -231,6 +232,22 @@ COLMAP_PROTOTYPES = {
 
 class ObjectSpace(C.Structure):      # include/lifcal_ba.h lifcal_ba_object_space
     _fields_ = [("rms", C.c_double * 3), ("max_abs", C.c_double * 3), ("rms_rel_depth", C.c_double), ("n_used", C.c_uint64), ("n_skipped", C.c_uint64)]
+
+
+class GroupStats(C.Structure):       # include/lifcal_ba.h lifcal_ba_group_stats: one 64-byte row per group
+    _fields_ = [("sum_x", C.c_double), ("sum_y", C.c_double), ("sum_xx", C.c_double), ("sum_yy", C.c_double), ("sum_w", C.c_double),
+                ("max_abs_x", C.c_double), ("max_abs_y", C.c_double), ("n", C.c_uint32), ("n_inliers", C.c_uint32)]
+
+
+# the same row as a numpy structured dtype (tables are arrays of it)
+GROUP_STATS_DTYPE = np.dtype([("sum_x", "<f8"), ("sum_y", "<f8"), ("sum_xx", "<f8"), ("sum_yy", "<f8"), ("sum_w", "<f8"),
+                              ("max_abs_x", "<f8"), ("max_abs_y", "<f8"), ("n", "<u4"), ("n_inliers", "<u4")])
+_gptr = C.POINTER(GroupStats)
+
+
+class ResidualReportIO(C.Structure):  # lifcal_ba_residual_report_io
+    _fields_ = [("inlier_threshold", C.c_double), ("ex", dptr), ("ey", dptr), ("weight", dptr), ("lens", uptr), ("lens_xy", dptr),
+                ("per_frame", _gptr), ("per_point", _gptr), ("per_lens", _gptr), ("total", GroupStats), ("seconds", C.c_double)]
 
 
 class DepthSampleCounts(C.Structure):   # include/lifcal_depth.h lifcal_depth_sample_counts
@@ -277,6 +294,8 @@ PROTOTYPES = {
     "lifcal_ba_set_fixed_frames": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint8)]),
     "lifcal_ba_default_covariance_options": (None, [C.POINTER(CovarianceOptions)]),
     "lifcal_ba_covariance": (C.c_int, [C.c_void_p, C.POINTER(CovarianceOptions), C.POINTER(CovarianceOut)]),
+    "lifcal_ba_residual_report": (C.c_int, [C.c_void_p, C.POINTER(ResidualReportIO)]),
+    "lifcal_ba_residual_groups": (C.c_int, [C.c_void_p, C.c_double, C.c_uint32, uptr, C.c_void_p]),
     "lifcal_ba_object_space_stats": (C.c_int, [C.c_void_p, C.c_uint64, dptr, dptr, dptr, uptr, uptr, dptr, dptr, C.POINTER(ObjectSpace)]),
     "lifcal_ba_solve_windowed": (C.c_int, [C.POINTER(Problem), C.POINTER(Options), C.c_uint32, C.c_uint32, C.c_void_p, C.POINTER(WindowReport), C.POINTER(C.c_uint32)]),
     "lifcal_ba_upload_parameters": (C.c_int, [C.c_void_p]),
@@ -299,6 +318,11 @@ PROTOTYPES = {
     "lifcal_ba_plan_shard": (C.c_int, [C.POINTER(Problem), C.POINTER(Partition), C.c_int32, C.POINTER(PlanInfo)]),
 }
 
+# host-only helpers of include/lifcal_ba.h outside the lifcal_ba_ / lifcal_init_ families
+HOST_PROTOTYPES = {
+    "lifcal_group_index": (C.c_int, [C.c_uint32, C.c_uint32, uptr, uptr, uptr]),
+}
+
 _lib = None
 
 
@@ -312,7 +336,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -73,6 +73,85 @@ class Covariance:
     cost: float = 0.0
 
 
+class GroupTable:
+    """One table of the residual report: `rows` is a structured array of capi.GROUP_STATS_DTYPE (sum_x, sum_y, sum_xx, sum_yy,
+    sum_w, max_abs_x, max_abs_y, n, n_inliers), one row per group; an empty group is an all-zero row and its derived values are NaN."""
+
+    def __init__(self, rows: np.ndarray):
+        self.rows = rows
+
+    def __len__(self):
+        return len(self.rows)
+
+    def __getitem__(self, name):
+        return self.rows[name]
+
+    def _per_n(self, v):
+        n = self.rows["n"].astype(np.float64)
+        with np.errstate(divide="ignore", invalid="ignore"):
+            return np.where(n > 0, v / n, np.nan)
+
+    @property
+    def n(self):
+        return self.rows["n"]
+
+    @property
+    def n_inliers(self):
+        return self.rows["n_inliers"]
+
+    @property
+    def mean_x(self):
+        return self._per_n(self.rows["sum_x"])
+
+    @property
+    def mean_y(self):
+        return self._per_n(self.rows["sum_y"])
+
+    @property
+    def rms_x(self):
+        """sqrt(sum e_x^2 / n): not mean-removed, as calcReprojectionError defines its std_x (reference :1097)"""
+        return np.sqrt(self._per_n(self.rows["sum_xx"]))
+
+    @property
+    def rms_y(self):
+        return np.sqrt(self._per_n(self.rows["sum_yy"]))
+
+    @property
+    def mean_weight(self):
+        return self._per_n(self.rows["sum_w"])
+
+
+@dataclass
+class ResidualReport:
+    """BundleAdjustment.residualReport: e = projected - observed in raw pixels at the device-resident parameters.
+
+    ex, ey, weight, lens   per observation in the caller's order (None without per_observation); weight is the Cauchy loss weight
+                           1 / (1 + |e|^2 / loss_scale^2), 1 when the loss is off; lens is the lens id, an index into lens_xy
+    lens_xy                (n_lenses, 2): the micro-lens centre (mcx, mcy) of every lens id
+    per_frame, per_point, per_lens, total   GroupTable (total has one row)
+    """
+    ex: Optional[np.ndarray]
+    ey: Optional[np.ndarray]
+    weight: Optional[np.ndarray]
+    lens: Optional[np.ndarray]
+    lens_xy: np.ndarray
+    per_frame: GroupTable
+    per_point: GroupTable
+    per_lens: GroupTable
+    total: GroupTable
+    inlier_threshold: float
+    seconds: float
+
+
+def sensor_cells(u, v, cell_px: float, raw_width: int, raw_height: int):
+    """Key for a residual map over the sensor (BundleAdjustment.residualGroups): the raw image is cut into square cells of cell_px
+    pixels, row-major; returns (key, n_keys, (cells_y, cells_x)).  Observations outside the image go to the nearest border cell."""
+    nx = max(1, int(np.ceil(raw_width / cell_px))); ny = max(1, int(np.ceil(raw_height / cell_px)))
+    cx = np.clip(np.floor(np.asarray(u, np.float64) / cell_px), 0, nx - 1).astype(np.uint32)
+    cy = np.clip(np.floor(np.asarray(v, np.float64) / cell_px), 0, ny - 1).astype(np.uint32)
+    return cy * np.uint32(nx) + cx, nx * ny, (ny, nx)
+
+
 class BundleAdjustment:
     """One bundle-adjustment problem resident on one MI355X (one rank of a point-sharded job)."""
 
@@ -130,6 +209,36 @@ class BundleAdjustment:
         x = np.zeros(n); y = np.zeros(n)
         _check(self.lib, self.lib.lifcal_ba_project_observations(self._h, capi.as_dptr(x), capi.as_dptr(y)), "lifcal_ba_project_observations")
         return x, y
+
+    def residualReport(self, inlierThreshold: float = 1.0, per_observation: bool = True) -> ResidualReport:
+        """The reprojection errors behind calcReprojectionError, per observation and summed by frame, 3D point and micro lens
+        (lifcal_ba_residual_report).  Every sum is taken in a fixed order: the report is bitwise reproducible."""
+        p = self.problem.struct
+        n, n_lenses = p.n_obs, self.info().n_lenses
+        io = capi.ResidualReportIO()
+        io.inlier_threshold = float(inlierThreshold)
+        ex = ey = w = lens = None
+        if per_observation:
+            ex = np.zeros(n); ey = np.zeros(n); w = np.zeros(n); lens = np.zeros(n, np.uint32)
+            io.ex, io.ey, io.weight, io.lens = capi.as_dptr(ex), capi.as_dptr(ey), capi.as_dptr(w), capi.as_uptr(lens)
+        lens_xy = np.zeros((n_lenses, 2))
+        tabs = [np.zeros(k, capi.GROUP_STATS_DTYPE) for k in (p.n_frames, p.n_points, n_lenses)]
+        io.lens_xy = capi.as_dptr(lens_xy)
+        io.per_frame, io.per_point, io.per_lens = (C.cast(t.ctypes.data, capi._gptr) for t in tabs)
+        _check(self.lib, self.lib.lifcal_ba_residual_report(self._h, C.byref(io)), "lifcal_ba_residual_report")
+        total = np.frombuffer(bytes(io.total), capi.GROUP_STATS_DTYPE).copy()
+        return ResidualReport(ex, ey, w, lens, lens_xy, GroupTable(tabs[0]), GroupTable(tabs[1]), GroupTable(tabs[2]), GroupTable(total),
+                              float(inlierThreshold), float(io.seconds))
+
+    def residualGroups(self, key, n_keys: int, inlierThreshold: float = 1.0) -> GroupTable:
+        """The statistics of residualReport for any grouping: key[i] < n_keys for every observation, in the caller's order
+        (lifcal_ba_residual_groups; see sensor_cells for a map over the sensor)."""
+        k = np.ascontiguousarray(key, np.uint32).reshape(-1)
+        if len(k) != self.problem.struct.n_obs:
+            raise LifcalError("residualGroups: one key per observation")
+        rows = np.zeros(int(n_keys), capi.GROUP_STATS_DTYPE)
+        _check(self.lib, self.lib.lifcal_ba_residual_groups(self._h, float(inlierThreshold), int(n_keys), capi.as_uptr(k), rows.ctypes.data), "lifcal_ba_residual_groups")
+        return GroupTable(rows)
 
     def set_fixed_frames(self, fixed=None):
         """hold the poses of the frames with fixed[f] != 0 constant in the following sweeps / solves (None frees all)"""

@@ -140,6 +140,12 @@ struct lifcal_ba_handle {
   uint8_t* frame_live_dev = nullptr;   // d.frame_live (frame is observed AND its pose is free), writable copy of the pointer
   std::vector<uint8_t> frame_live_host;   // ... and its host copy (lifcal_ba_covariance restores it after holding the gauge frame)
   double *cov_C = nullptr, *cov_Cp = nullptr, *cov_Zd = nullptr, *cov_Y = nullptr, *cov_G = nullptr, *cov_Zb = nullptr, *cov_fail = nullptr;   // lifcal_ba_covariance, allocated at its first call
+  // lifcal_ba_residual_report (residuals.hpp), built at its first call: per-observation buffers in the caller's order, the tile
+  // payload's input indices, CSR indices by frame / point / lens ([0], [1], [2]), the one-segment index of the total, the rows
+  bool res_ready = false;
+  double *res_ex = nullptr, *res_ey = nullptr, *res_w = nullptr;
+  uint32_t *res_lens = nullptr, *res_src1 = nullptr, *res_src2 = nullptr, *res_off[3] = {nullptr, nullptr, nullptr}, *res_idx[3] = {nullptr, nullptr, nullptr}, *res_tot_off = nullptr;
+  lifcal_ba_group_stats* res_rows = nullptr;
   bool trace = false;            // LIFCAL_TRACE=1: one stderr line per host decision of the LM loop, tagged with the rank
   double* Lpanel = nullptr; size_t bandw_lds = 0, backw_lds = 0; bool bandw_ok = false;
   CrPlan cr; bool use_cr = false;   // block odd-even reduction (bandchol3.hpp): long sequences
@@ -1518,6 +1524,9 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 
 // covariance of the calibrated parameters: kernels and lifcal_ba_covariance (include/lifcal_ba.h)
 #include "covariance.hpp"
+
+// residual report: per-observation errors and their sums by frame, point, lens or caller key (include/lifcal_ba.h)
+#include "residuals.hpp"
 
 // depth-map sampling, back-projection to metric 3D and the object-space comparison (include/lifcal_depth.h, include/lifcal_ba.h)
 #include "depth.hpp"

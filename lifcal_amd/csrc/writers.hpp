@@ -223,4 +223,21 @@ int lifcal_write_camera_coordinates_ply(const char* dir, int32_t frame_id, uint6
   return lifcal_io::write_cloud_ply((std::string(dir) + name).c_str(), n_points, xyz);
 }
 
+int lifcal_write_group_stats_csv(const char* path, const char* id_header, uint64_t n, const int32_t* ids, const double* xy, const lifcal_ba_group_stats* rows) {
+  if (!path || !id_header || (n && !rows)) return LIFCAL_BA_ERR_INVALID_ARG;
+  FILE* f = std::fopen(path, "w");
+  if (!f) return LIFCAL_BA_ERR_INVALID_ARG;
+  std::fprintf(f, "%s%s,n,n_inliers,mean_x,mean_y,rms_x,rms_y,max_abs_x,max_abs_y,mean_weight\n", id_header, xy ? ",x,y" : "");
+  for (uint64_t k = 0; k < n; ++k) {
+    const lifcal_ba_group_stats& r = rows[k];
+    if (!r.n) continue;
+    const double m = (double)r.n;
+    std::fprintf(f, "%lld", ids ? (long long)ids[k] : (long long)k);
+    if (xy) std::fprintf(f, ",%f,%f", xy[2 * k], xy[2 * k + 1]);
+    std::fprintf(f, ",%u,%u,%f,%f,%f,%f,%f,%f,%f\n", r.n, r.n_inliers, r.sum_x / m, r.sum_y / m, std::sqrt(r.sum_xx / m), std::sqrt(r.sum_yy / m),
+                 r.max_abs_x, r.max_abs_y, r.sum_w / m);
+  }
+  return std::fclose(f) == 0 ? 0 : LIFCAL_BA_ERR_INVALID_ARG;
+}
+
 }  // extern "C"

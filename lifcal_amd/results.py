@@ -104,3 +104,26 @@ def storeCameraCoordinates(dir_results: str, folder: str, frame_ids, fr, xyz):
     for f, fid in enumerate(np.asarray(frame_ids).reshape(-1)):
         sel = np.ascontiguousarray(p[fr == f])
         _ok(lib.lifcal_write_camera_coordinates_ply(d.encode(), int(fid), len(sel), capi.as_dptr(sel)), "storeCameraCoordinates")
+
+
+def _group_csv(path: str, id_header: str, table, ids=None, xy=None):
+    rows = np.ascontiguousarray(table.rows if hasattr(table, "rows") else table, capi.GROUP_STATS_DTYPE)
+    ids = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1)
+    xy = None if xy is None else np.ascontiguousarray(xy, np.float64).reshape(-1)
+    if (ids is not None and len(ids) != len(rows)) or (xy is not None and len(xy) != 2 * len(rows)):
+        raise LifcalError("storeGroupStatsCsv: one id and one (x, y) per row")
+    _ok(capi.load_library().lifcal_write_group_stats_csv(path.encode(), id_header.encode(), len(rows), ids.ctypes.data_as(capi._iptr) if ids is not None else None,
+                                                         capi.as_dptr(xy) if xy is not None else None, rows.ctypes.data), "storeGroupStatsCsv")
+
+
+def storeGroupStatsCsv(path: str, id_header: str, table, ids=None, xy=None):
+    """one table of BundleAdjustment.residualReport / residualGroups as CSV (lifcal_write_group_stats_csv): empty groups are left out"""
+    _group_csv(path, id_header, table, ids, xy)
+
+
+def storeResidualReport(dir_results: str, frame_ids, report):
+    """residualsPerFrame.csv (frame.id per row), residualsPerPoint.csv and residualsPerLens.csv (with the lens centres) of a
+    BundleAdjustment.residualReport; no reference counterpart."""
+    _group_csv(os.path.join(dir_results, "residualsPerFrame.csv"), "frame", report.per_frame, ids=frame_ids)
+    _group_csv(os.path.join(dir_results, "residualsPerPoint.csv"), "point", report.per_point)
+    _group_csv(os.path.join(dir_results, "residualsPerLens.csv"), "lens", report.per_lens, xy=report.lens_xy)
