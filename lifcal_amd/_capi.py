@@ -279,6 +279,31 @@ DEPTH_PROTOTYPES = {
     "lifcal_depth_back_project_maps": (C.c_int, [C.c_void_p, C.POINTER(DepthCamera), C.POINTER(DepthMapsArgs)]),
 }
 
+class ResectProblem(C.Structure):    # include/lifcal_resect.h lifcal_resect_problem
+    _fields_ = [("n_obs", C.c_uint32), ("n_frames", C.c_uint32), ("n_points", C.c_uint32), ("reserved", C.c_uint32),
+                ("u", dptr), ("v", dptr), ("mcx", dptr), ("mcy", dptr), ("pt", uptr), ("fr", uptr),
+                ("cam", dptr), ("pts", dptr), ("views", dptr),
+                ("spx", C.c_double), ("spy", C.c_double), ("scale", C.c_double), ("config", C.c_uint32)]
+
+
+class ResectFrame(C.Structure):      # lifcal_resect_frame: one 288-byte row per frame
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_radius", C.c_double), ("final_gradient_max_norm", C.c_double),
+                ("H", C.c_double * 21), ("g", C.c_double * 6), ("sum_xx", C.c_double), ("sum_yy", C.c_double),
+                ("n_obs", C.c_uint32), ("n_inliers", C.c_uint32),
+                ("iterations", C.c_int32), ("successful_steps", C.c_int32), ("unsuccessful_steps", C.c_int32), ("termination", C.c_int32)]
+
+
+# the same row as a numpy structured dtype (the table of a call is an array of it)
+RESECT_FRAME_DTYPE = np.dtype([("initial_cost", "<f8"), ("final_cost", "<f8"), ("final_radius", "<f8"), ("final_gradient_max_norm", "<f8"),
+                               ("H", "<f8", (21,)), ("g", "<f8", (6,)), ("sum_xx", "<f8"), ("sum_yy", "<f8"),
+                               ("n_obs", "<u4"), ("n_inliers", "<u4"),
+                               ("iterations", "<i4"), ("successful_steps", "<i4"), ("unsuccessful_steps", "<i4"), ("termination", "<i4")])
+
+# every symbol include/lifcal_resect.h declares
+RESECT_PROTOTYPES = {
+    "lifcal_resect_frames": (C.c_int, [C.POINTER(ResectProblem), C.POINTER(Options), C.c_double, C.c_void_p, dptr]),
+}
+
 # every symbol include/lifcal_ba.h declares: name -> (restype, argtypes)
 PROTOTYPES = {
     "lifcal_ba_default_options": (None, [C.POINTER(Options)]),
@@ -336,7 +361,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

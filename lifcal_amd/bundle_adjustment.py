@@ -295,6 +295,26 @@ class BundleAdjustment:
                                                                capi.as_dptr(ref), capi.as_dptr(proj), C.byref(st)), "lifcal_ba_object_space_stats")
         return st, ref, proj
 
+    def resectFrames(self, views0=None, observations=None, options: Optional[capi.Options] = None, inlierThreshold: float = 1.0):
+        """Resect frames against the handle's current (device-resident) camera and points, which stay constant
+        (lifcal_amd.resection.resectFrames).  observations: (u, v, mcx, mcy, pt, fr) of the frames to localise, fr counting them
+        from 0, with their start poses views0; None: the problem's own observations (and, without views0, its current poses).
+        The handle and its parameters are left as they are."""
+        from .resection import resectFrames
+        self.download_parameters()
+        pr = self.problem
+        if observations is None:
+            observations = (pr.u, pr.v, pr.mcx, pr.mcy, pr.pt, pr.fr)
+            if views0 is None:
+                views0 = pr.views
+        if views0 is None:
+            raise LifcalError("resectFrames: new observations need start poses")
+        u, v, mcx, mcy, pt, fr = observations
+        if options is None:
+            options = capi.Options.from_buffer_copy(self.options); options.world_size = 1; options.rank = 0; options.precision = 0
+        return resectFrames(pr.cam, pr.pts, u, v, mcx, mcy, pt, fr, views0, pr.struct.config, pr.struct.spx, pr.struct.scale, spy=pr.struct.spy,
+                            options=options, inlierThreshold=inlierThreshold)
+
     # -- the benchmarked unit ------------------------------------------------------------------
     def sweep(self, radius: float = 1e4, want_matrices: bool = False):
         """One Jacobian+Schur sweep; returns a namespace with cost, gradient_max_norm, seconds and,
