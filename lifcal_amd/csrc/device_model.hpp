@@ -22,6 +22,18 @@ namespace lifcal {
 
 #define LIFCAL_DEV __device__ __forceinline__
 
+// Store of a WRITE-ONCE output: a value that no thread of the same launch reads back (a later kernel does).  The line is not
+// kept in the L2 beyond the write, so it is on its way to HBM while the kernel still runs instead of being written back at the
+// kernel's end.  One value, or two values at a 16-byte aligned address as one 16-byte store.
+typedef double stream_d2 __attribute__((ext_vector_type(2)));
+LIFCAL_DEV void store_stream(double* p, double v) {
+  asm volatile("global_store_dwordx2 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
+}
+LIFCAL_DEV void store_stream(double* p, double v0, double v1) {
+  const stream_d2 v{v0, v1};
+  asm volatile("global_store_dwordx4 %0, %1, off sc1\n\ts_nop 1" :: "v"(p), "v"(v) : "memory");
+}
+
 constexpr int NCMAX = 9;       // 5 + 2 radial + 2 tangential live camera slots
 constexpr int LENS_STRIDE = 16;  // doubles per lens-table entry
 constexpr int FRAME_STRIDE = 16; // doubles per frame-table entry

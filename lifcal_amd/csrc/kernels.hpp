@@ -405,26 +405,22 @@ __global__ __launch_bounds__(256) void k_sweep(Dev d) {
 
 // one column of the reduced system: ceres LevenbergMarquardtStrategy diagonal (clamp(sigma^2 h) / (radius sigma^2) in the
 // unscaled space), rhs = -g_B + W^T U^-1 g into the rhs arrow row, identity for columns that are not solved for
+// Every input of the column is requested before the first one is used (one round trip to memory instead of a chain of four:
+// live flag -> sigma -> diagonal of the Hessian -> diagonal of S); the arithmetic is the one of the branches it replaces.
 LIFCAL_DEV double finalize_column(const Dev& d, uint32_t t, double radius) {
-  const uint32_t F6 = 6 * d.F;
-  bool live;
-  if (t < F6) live = d.use_poses && d.frame_live[t / 6];
-  else if (t < F6 + 3 * d.Q) live = true;
-  else live = d.camc->chm[t - F6 - 3 * d.Q] != 0.0;
+  const uint32_t F6 = 6 * d.F, A0 = F6 + 3 * d.Q;
   double* diag = s_addr(d, t, t);
   double* rhs = d.Sarrow + (size_t)d.NA * d.ld;  // extra arrow row carries the right-hand side
-  if (live) {
-    const double s = d.sig_red[t];
-    const double lam = fmin(fmax(d.hdiag[t] * s * s, d.lm_min), d.lm_max) / (lm_radius(d, radius) * s * s);
-    d.lam_red[t] = lam;
-    *diag += lam;
-    rhs[t] = -d.gB[t] + d.rhsacc[t];
-  } else {
-    d.lam_red[t] = 0.0;
-    *diag = 1.0;
-    rhs[t] = 0.0;
-  }
-  return fabs(d.gB[t]);
+  const uint32_t fl = t < F6 ? (uint32_t)d.frame_live[t / 6] : 1u;
+  const double ch = t >= A0 ? d.camc->chm[t - A0] : 1.0;
+  const double s = d.sig_red[t], h = d.hdiag[t], g = d.gB[t], ra = d.rhsacc[t], dg = *diag;
+  const double rad = lm_radius(d, radius);
+  const bool live = t < F6 ? (d.use_poses && fl) : ch != 0.0;
+  const double lam = live ? fmin(fmax(h * s * s, d.lm_min), d.lm_max) / (rad * s * s) : 0.0;
+  d.lam_red[t] = lam;
+  *diag = live ? dg + lam : 1.0;
+  rhs[t] = live ? -g + ra : 0.0;
+  return fabs(g);
 }
 
 }  // namespace lifcal
@@ -820,9 +816,15 @@ __global__ void k_det_sum(const double* slots, uint32_t n_wg, uint32_t K, double
 // and step scalars that the NEXT sweep accumulates into; nobody reads it any more)
 constexpr uint32_t FIN_ZERO_PER_WG = 256 * 4;   // doubles per zero-filling workgroup the host sizes the grid with
 __global__ void k_finalize(Dev d, double radius, uint32_t n_fin, double* zero, uint32_t n_zero) {
-  if (blockIdx.x >= n_fin) {
-    const uint32_t n_threads = (gridDim.x - n_fin) * blockDim.x;
-    for (uint32_t i = (blockIdx.x - n_fin) * blockDim.x + threadIdx.x; i < n_zero; i += n_threads) zero[i] = 0.0;
+  if (blockIdx.x >= n_fin) {   // (the finalising workgroups have the lowest indices: they are dispatched first)
+    const uint32_t n_threads = (gridDim.x - n_fin) * blockDim.x, t0 = (blockIdx.x - n_fin) * blockDim.x + threadIdx.x;
+    // 16-byte stores from the first 16-byte aligned double on; the (at most two) doubles around them singly
+    const uint32_t odd = (uint32_t)(((uintptr_t)zero >> 3) & 1u), head = odd < n_zero ? odd : n_zero;
+    const uint32_t n2 = (n_zero - head) / 2;
+    double2* z2 = reinterpret_cast<double2*>(zero + head);
+    for (uint32_t i = t0; i < n2; i += n_threads) z2[i] = double2{0.0, 0.0};
+    if (t0 == 0 && head) zero[0] = 0.0;
+    if (t0 == 0 && head + 2 * n2 < n_zero) zero[n_zero - 1] = 0.0;
     return;
   }
   const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;

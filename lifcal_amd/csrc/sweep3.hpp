@@ -104,7 +104,7 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
           const double w0 = z[0], w1 = z[zs], w2 = z[2 * zs];
           if (cc0 >= 6 * nf) {
             double* ga = d.ptacc + (size_t)pidl[lp] * 36 + 9 + (cc0 - 6 * nf);
-            ga[0] = w0; ga[NCMAX] = w1; ga[2 * NCMAX] = w2;
+            store_stream(ga, w0); store_stream(ga + NCMAX, w1); store_stream(ga + 2 * NCMAX, w2);
           }
           z[0] = acc[0] * w0; z[zs] = acc[1] * w0 + acc[3] * w1; z[2 * zs] = acc[2] * w0 + acc[4] * w1 + acc[5] * w2;
         }
@@ -440,9 +440,8 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
           }
         }
         if (mode == 0) {
-          { double* ga = d.Av + (size_t)gidx * 6;
-#pragma unroll
-            for (int k = 0; k < 6; ++k) ga[k] = A[k]; }
+          { double* ga = d.Av + (size_t)gidx * 6;   // 48 bytes per lane, 16-byte aligned: three 16-byte stores
+            store_stream(ga, A[0], A[1]); store_stream(ga + 2, A[2], A[3]); store_stream(ga + 4, A[4], A[5]); }
 #pragma unroll
           for (int i = 0; i < 3; ++i) {
             atomicAdd(acc + 6 + i, R[i] * bv[0] + R[3 + i] * bv[1] + R[6 + i] * bv[2]);
@@ -481,7 +480,7 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
         double U0 = acc[0], U1 = acc[1], U2 = acc[2], U3 = acc[3], U4 = acc[4], U5 = acc[5];
         if (mode == 1) {
           double* ga = d.ptacc + (size_t)p * 36;
-          ga[0] = U0; ga[3] = U3; ga[5] = U5;
+          store_stream(ga, U0); store_stream(ga + 3, U3); store_stream(ga + 5, U5);
         } else {
           const double g0 = acc[6], g1 = acc[7], g2 = acc[8];
           double lam[3];
@@ -504,10 +503,16 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
           double* gu = d.Uinv + 9 * (size_t)p;
           const double v00 = i00 * i00 + m10 * m10 + m20 * m20, v01 = m10 * i11 + m20 * m21, v02 = m20 * i22;
           const double v11 = i11 * i11 + m21 * m21, v12 = m21 * i22, v22 = i22 * i22;
-          gu[0] = v00; gu[1] = v01; gu[2] = v02; gu[3] = v01; gu[4] = v11; gu[5] = v12; gu[6] = v02; gu[7] = v12; gu[8] = v22;
-          double* gl = d.lamP + 3 * (size_t)p; gl[0] = lam[0]; gl[1] = lam[1]; gl[2] = lam[2];
-          double* ga = d.ptacc + (size_t)p * 36;
-          ga[6] = g0; ga[7] = g1; ga[8] = g2;
+          {
+            const double vu[9] = {v00, v01, v02, v01, v11, v12, v02, v12, v22};
+#pragma unroll
+            for (int k = 0; k < 9; ++k) store_stream(gu + k, vu[k]);
+          }
+          double* gl = d.lamP + 3 * (size_t)p;
+          double* ga = d.ptacc + (size_t)p * 36 + 6;
+#pragma unroll
+          for (int k = 0; k < 3; ++k) store_stream(gl + k, lam[k]);
+          store_stream(ga, g0); store_stream(ga + 1, g1); store_stream(ga + 2, g2);
           const double gm = fmax(fabs(g0), fmax(fabs(g1), fabs(g2)));
           atomicMax((unsigned long long*)(misc + 2), (unsigned long long)__double_as_longlong(gm));
           acc[0] = i00; acc[1] = m10; acc[2] = m20; acc[3] = i11; acc[4] = m21; acc[5] = i22;
@@ -773,6 +778,27 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
   // =======================================================================================================================
   lds_barrier();
   STAMP(10);
+  // The words EVERY block adds to — camera x camera block, camera entries of the three vectors, the scalars — are final here
+  // (the fold below touches pose entries only) and go out first: their device-scope atomics queue up behind those of all other
+  // blocks, which finish within a few percent of each other, and that chain then runs under the fold and the issue of the block's
+  // own entries instead of behind them (profiles/sweep_tail: 6.0 of the flush's 8.6 us per step belong to these ~75 words).
+  if (!det) {
+    const uint32_t F6 = 6 * d.F, camrow = 3 * d.Q, camcol = F6 + 3 * d.Q;
+    if (mode == 0 && tid < (uint32_t)NCC) {
+      uint32_t i = 0; while ((i + 1) * (i + 2) / 2 <= tid) ++i;
+      const uint32_t j = tid - i * (i + 1) / 2;
+      atomicAdd(d.Sarrow + (size_t)(camrow + i) * d.ld + camcol + j, Scc[tid]);
+    }
+    if (tid < (uint32_t)NC) {
+      atomicAdd(d.hdiag + camcol + tid, vhd[6 * NFm + tid]);
+      if (mode == 0) { atomicAdd(d.gB + camcol + tid, vgB[6 * NFm + tid]); atomicAdd(d.rhsacc + camcol + tid, vrhs[6 * NFm + tid]); }
+    }
+    if (mode == 0 && tid == 0) {
+      atomicAdd(d.scal + SCAL_COST, misc[0]);
+      if (misc[1] != 0.0) atomicAdd(d.scal + SCAL_BAD_U, misc[1]);
+      atomicMax((unsigned long long*)(d.scal + SCAL_GMAX0 + d.rank), *(unsigned long long*)(misc + 2));
+    }
+  }
   for (uint32_t i = tid; i < FRV * nf; i += NT) {
     const uint32_t v = i / nf, lf = i % nf;
     double sacc = 0.0;
@@ -800,9 +826,14 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
     return;
   }
   const uint32_t F6 = 6 * d.F, camrow = 3 * d.Q, camcol = F6 + 3 * d.Q;
+  // the block's own entries (the words every block adds to went out in front of the fold): vectors, camera x pose rows, then the band
   for (uint32_t i = tid; i < 6 * nf; i += NT) atomicAdd(d.hdiag + 6 * flo + i, vhd[i]);
-  if (tid < (uint32_t)NC) atomicAdd(d.hdiag + camcol + tid, vhd[6 * NFm + tid]);
   if (mode == 0) {
+    for (uint32_t i = tid; i < 6 * nf; i += NT) { atomicAdd(d.gB + 6 * flo + i, vgB[i]); atomicAdd(d.rhsacc + 6 * flo + i, vrhs[i]); }
+    for (uint32_t i = tid; i < (uint32_t)NC * 6 * nf; i += NT) {
+      const uint32_t j = i / (6 * nf), cidx = i % (6 * nf);
+      atomicAdd(d.Sarrow + (size_t)(camrow + j) * d.ld + 6 * flo + cidx, Scp[(size_t)j * 6 * NFm + cidx]);
+    }
     const uint32_t npp = nf * (nf + 1) / 2;
     for (uint32_t i = tid; i < npp * 36; i += NT) {
       const uint32_t blk = i / 36, e = i % 36;
@@ -812,22 +843,6 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
       const uint32_t bb = blk - a * (a + 1) / 2, dd = a - bb;
       const double v = Spp[i];
       if (dd <= d.bw && v != 0.0 && !(dd == 0 && (e % 6) > (e / 6))) atomicAdd(d.Sband + ((size_t)(flo + a) * (d.bw + 1) + dd) * 36 + e, v);
-    }
-    for (uint32_t i = tid; i < (uint32_t)NC * 6 * nf; i += NT) {
-      const uint32_t j = i / (6 * nf), cidx = i % (6 * nf);
-      atomicAdd(d.Sarrow + (size_t)(camrow + j) * d.ld + 6 * flo + cidx, Scp[(size_t)j * 6 * NFm + cidx]);
-    }
-    if (tid < (uint32_t)NCC) {
-      uint32_t i = 0; while ((i + 1) * (i + 2) / 2 <= tid) ++i;
-      const uint32_t j = tid - i * (i + 1) / 2;
-      atomicAdd(d.Sarrow + (size_t)(camrow + i) * d.ld + camcol + j, Scc[tid]);
-    }
-    for (uint32_t i = tid; i < 6 * nf; i += NT) { atomicAdd(d.gB + 6 * flo + i, vgB[i]); atomicAdd(d.rhsacc + 6 * flo + i, vrhs[i]); }
-    if (tid < (uint32_t)NC) { atomicAdd(d.gB + camcol + tid, vgB[6 * NFm + tid]); atomicAdd(d.rhsacc + camcol + tid, vrhs[6 * NFm + tid]); }
-    if (tid == 0) {
-      atomicAdd(d.scal + SCAL_COST, misc[0]);
-      if (misc[1] != 0.0) atomicAdd(d.scal + SCAL_BAD_U, misc[1]);
-      atomicMax((unsigned long long*)(d.scal + SCAL_GMAX0 + d.rank), *(unsigned long long*)(misc + 2));
     }
   }
 #ifdef LIFCAL_STAMPS
