@@ -355,6 +355,26 @@ typedef struct lifcal_ba_info {
 } lifcal_ba_info;
 int lifcal_ba_get_info(lifcal_ba_handle* h, lifcal_ba_info* out);
 
+/* One Levenberg-Marquardt step, read back (tests: the step is checked against the damped normal equations, not inferred from
+ * parameters).  The last operation on the handle must have been lifcal_ba_sweep(h, radius, ...): the step is taken on that sweep's
+ * S | rhs, at that radius.  Runs what an iteration of lifcal_ba_solve runs between its sweep and its decision — the linear solve of
+ * the reduced system on the route create() chose, the candidate point (reduced part, back-substitution of the points), its cost —
+ * and leaves the handle as a rejected step leaves it: parameters unchanged, candidate arrays written, the sweep's block consumed
+ * (a second call without a new sweep is refused).  LIFCAL_BA_ERR_INVALID_ARG otherwise, and with world_size > 1. */
+typedef struct lifcal_ba_step_out {
+  double* delta_reduced;   /* [n_reduced] or NULL: canonical order of lifcal_ba_sweep_out; dead and fixed slots 0              */
+  double* delta_points;    /* [3P] or NULL: step of every refined, observed point (eliminated or promoted), 0 elsewhere         */
+  double* lambda_reduced;  /* [n_reduced] or NULL: the LM diagonal the step was damped with, same order; 0 on dead slots        */
+  double* lambda_points;   /* [3P] or NULL: ... of the points, as delta_points                                                  */
+  double gtd, ddd;         /* g . delta and sum lambda_i delta_i^2 over all columns: the model cost change is (ddd - gtd) / 2     */
+  double step2, x2;        /* |x_candidate - x|^2 and |x|^2 over the blocks the step-size test counts                           */
+  double cand_cost;        /* cost at x + delta                                                                                 */
+  double chol_fail;        /* != 0: a pivot of the factorisation was not positive                                               */
+  int32_t route;           /* 0 global-memory chain, 1 LDS chain, 2 two-ended (twisted) chain, 3 block odd-even reduction       */
+  int32_t panel_in_lds;    /* route 0: the panel of the chain lives in LDS (1) or in global memory (0)                          */
+} lifcal_ba_step_out;
+int lifcal_ba_debug_step(lifcal_ba_handle* h, lifcal_ba_step_out* out);
+
 void lifcal_ba_destroy(lifcal_ba_handle* h);
 const char* lifcal_ba_strerror(int code);
 const char* lifcal_ba_last_error(void);

@@ -68,6 +68,13 @@ class Info(C.Structure):
                 ("device_bytes", C.c_uint64), ("stream", C.c_void_p)]
 
 
+class StepOut(C.Structure):          # lifcal_ba_step_out
+    _fields_ = [("delta_reduced", dptr), ("delta_points", dptr), ("lambda_reduced", dptr), ("lambda_points", dptr),
+                ("gtd", C.c_double), ("ddd", C.c_double), ("step2", C.c_double), ("x2", C.c_double),
+                ("cand_cost", C.c_double), ("chol_fail", C.c_double),
+                ("route", C.c_int32), ("panel_in_lds", C.c_int32)]
+
+
 class Profile(C.Structure):
     _fields_ = [("n_sweeps", C.c_uint32), ("special_points", C.c_double), ("ms_accumulate", C.c_double),
                 ("ms_schur", C.c_double), ("ms_total", C.c_double), ("ms_exchange", C.c_double), ("n_sampled", C.c_uint32)]
@@ -330,6 +337,7 @@ PROTOTYPES = {
     "lifcal_ba_comm_unique_id": (C.c_int, [C.c_void_p]),
     "lifcal_ba_comm_init_rccl": (C.c_int, [C.c_void_p, C.c_void_p]),
     "lifcal_ba_get_info": (C.c_int, [C.c_void_p, C.POINTER(Info)]),
+    "lifcal_ba_debug_step": (C.c_int, [C.c_void_p, C.POINTER(StepOut)]),
     "lifcal_ba_destroy": (None, [C.c_void_p]),
     "lifcal_init_plenoptic": (C.c_int, [C.POINTER(InitProblem), C.c_int32, C.POINTER(InitResult)]),
     "lifcal_init_plenoptic_recalibration": (C.c_int, [C.c_double, C.c_double, C.POINTER(InitResult)]),

@@ -334,6 +334,24 @@ class BundleAdjustment:
         res.n_reduced = out.n_reduced; res.n_promoted = out.n_promoted
         return res
 
+    def debug_step(self):
+        """One LM step on the S | rhs of the sweep() just made, read back (lifcal_ba_debug_step): returns a namespace with
+        delta_reduced (canonical order of sweep().S), delta_points (3P), lambda_reduced / lambda_points (the LM diagonal the step
+        was damped with, same orders), the step scalars gtd, ddd, step2, x2, cand_cost, chol_fail,
+        route (0 global-memory chain, 1 LDS chain, 2 twisted, 3 block odd-even reduction) and panel_in_lds.  The parameters stay
+        as they are; anything but a sweep() in front of the call raises LifcalError (code LIFCAL_BA_ERR_INVALID_ARG)."""
+        out = capi.StepOut()
+        res = type("Step", (), {})()
+        n, P3 = self.info().n_reduced, 3 * self.problem.struct.n_points
+        res.delta_reduced = np.zeros(n); res.delta_points = np.zeros(P3); res.lambda_reduced = np.zeros(n); res.lambda_points = np.zeros(P3)
+        out.delta_reduced, out.delta_points = capi.as_dptr(res.delta_reduced), capi.as_dptr(res.delta_points)
+        out.lambda_reduced, out.lambda_points = capi.as_dptr(res.lambda_reduced), capi.as_dptr(res.lambda_points)
+        _check(self.lib, self.lib.lifcal_ba_debug_step(self._h, C.byref(out)), "lifcal_ba_debug_step")
+        for k in ("gtd", "ddd", "step2", "x2", "cand_cost", "chol_fail"):
+            setattr(res, k, float(getattr(out, k)))
+        res.route = int(out.route); res.panel_in_lds = bool(out.panel_in_lds)
+        return res
+
     def sweep_enqueue(self, radius: float = 1e4):
         """Enqueue one sweep on the handle's stream without a host round trip (timing loops)."""
         rc = self.lib.lifcal_ba_sweep_enqueue(self._h, float(radius))

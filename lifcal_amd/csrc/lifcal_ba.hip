@@ -134,6 +134,7 @@ struct lifcal_ba_handle {
   Xch xch{}; bool xch_ok = false, force_exchange = false;   // slab exchange of the reduced block (multi-GPU, no promoted points)
   void* comm = nullptr; bool comm_borrowed = false;   // RCCL communicator (borrowed: it belongs to another handle, see lifcal_ba_solve_windowed)
   double last_cost = 0, last_gmax = 0;
+  bool swept = false;            // the bound block holds S | rhs of a lifcal_ba_sweep that nothing has consumed or outdated (lifcal_ba_debug_step)
   size_t chol_lds = 0;
   double* ls_buf = nullptr;      // line search scalars, all-reduced: [0] |step|^2 [1] |x|^2 [2] grad . dir (each: this rank's points; rank 0 adds the replicated camera + pose part)
   double* dirmax_buf = nullptr;  // [0..63] per-rank max |point step| (one-hot slots, all-reduced), [64] max |reduced step| (replicated)
@@ -377,6 +378,7 @@ int launch_blocks(lifcal_ba_handle* h, double radius, int mode) {
 // one Jacobian + Schur sweep at the current point and the given trust-region radius
 int launch_sweep(lifcal_ba_handle* h, double radius) {
   Dev& d = h->d;
+  h->swept = false;
   if (h->prof_in_span() && h->prof_seen == 0) HIP_TRY(hipEventRecord(h->prof_span0, h->stream));   // the span opens with the first profiled sweep ...
   if (int rc = ensure_current_tables(h)) return rc;
   if (!h->sigma_valid) {
@@ -648,6 +650,7 @@ int upload_parameters(lifcal_ba_handle* h) {
   HIP_TRY(hipStreamSynchronize(h->stream));   // (cam is a stack array, the caller's arrays may change after the call)
   ss_upload(&h->ss);
   h->sigma_valid = false;
+  h->swept = false;
   return 0;
 }
 
@@ -1149,6 +1152,7 @@ int lifcal_ba_set_fixed_frames(lifcal_ba_handle* h, const uint8_t* fixed) {
   if (!live.empty()) HIP_TRY(hipMemcpy(h->frame_live_dev, live.data(), live.size(), hipMemcpyHostToDevice));
   h->frame_live_host = live;
   h->sigma_valid = false;   // the Jacobi scaling is fixed at the first sweep of a solve: a new column set starts a new solve
+  h->swept = false;
   return 0;
 }
 
@@ -1309,6 +1313,56 @@ int lifcal_ba_sweep(lifcal_ba_handle* h, double radius, lifcal_ba_sweep_out* out
     }
   }
   if (!std::isfinite(cost)) return LIFCAL_BA_ERR_NUMERIC;
+  h->swept = true;
+  return 0;
+}
+
+// One LM step on the block the last lifcal_ba_sweep left, read back: what an iteration of the host loop runs between its sweep and
+// its decision, and nothing else.  The handle is left as after a rejected step (candidate arrays and tables written, block consumed).
+int lifcal_ba_debug_step(lifcal_ba_handle* h, lifcal_ba_step_out* out) {
+  if (!h || !out) return LIFCAL_BA_ERR_INVALID_ARG;
+  if (h->opt.world_size > 1) { g_last_error = "lifcal_ba_debug_step: one rank only"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  if (!h->swept) { g_last_error = "lifcal_ba_debug_step: the last operation on the handle was not lifcal_ba_sweep"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  Dev& d = h->d;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  h->swept = false;   // (the factorisation works in place: the block no longer holds S)
+  if (int rc = launch_linear_solve(h)) return rc;
+  if (int rc = launch_candidate(h)) return rc;
+  StepScalars st;
+  if (int rc = read_step_scalars(h, &st)) return rc;
+  out->gtd = st.gtd; out->ddd = st.ddd; out->step2 = st.step2; out->x2 = st.x2; out->cand_cost = st.cand_cost; out->chol_fail = st.chol_fail;
+  out->route = h->use_cr ? 3 : (h->bandw_ok && h->twisted) ? 2 : h->bandw_ok ? 1 : 0;   // the branches of launch_linear_solve
+  out->panel_in_lds = d.panel_g == nullptr ? 1 : 0;
+  const uint32_t F6 = 6 * d.F, Q3 = 3 * d.Q, nci = d.n_red, ncan = h->plan.n_red_canon;
+  std::vector<double> dr(nci);
+  if (nci) HIP_TRY(hipMemcpy(dr.data(), d.delta_red, dr.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<double> lr(nci);
+  if (nci && (out->lambda_reduced || out->lambda_points)) HIP_TRY(hipMemcpy(lr.data(), d.lam_red, lr.size() * 8, hipMemcpyDeviceToHost));
+  // internal index (poses | promoted | camera) -> canonical index (camera 17 | poses | promoted), as lifcal_ba_sweep
+  auto canon = [&](uint32_t t) -> uint32_t { if (t < F6) return 17 + t; if (t < F6 + Q3) return 17 + F6 + (t - F6); return t - F6 - Q3; };
+  auto put_reduced = [&](double* dst, const std::vector<double>& src) {
+    if (!dst) return;
+    std::fill(dst, dst + ncan, 0.0);
+    for (uint32_t t = 0; t < nci; ++t) dst[canon(t)] = src[t];
+  };
+  put_reduced(out->delta_reduced, dr);
+  put_reduced(out->lambda_reduced, lr);
+  // points: the buffer of the eliminated points this rank works (the rule of lifcal_ba_sweep's point outputs), the reduced entries of the promoted ones
+  auto put_points = [&](double* dst, const double* dev, const std::vector<double>& red) -> int {
+    if (!dst) return 0;
+    std::fill(dst, dst + 3 * (size_t)d.P, 0.0);
+    if (!d.use_points || !d.P) return 0;
+    std::vector<double> dp(3 * (size_t)d.P);
+    HIP_TRY(hipMemcpy(dp.data(), dev, dp.size() * 8, hipMemcpyDeviceToHost));
+    for (uint32_t q = 0; q < d.P; ++q) {
+      const bool mine = h->plan.promoted[q] < 0 && h->plan.owner[q] == h->opt.rank && (h->plan.pt_nslots[q] > 0 || (h->plan.pt_cons0.size() > q + 1 && h->plan.pt_cons0[q + 1] > h->plan.pt_cons0[q]));
+      if (mine) for (int k = 0; k < 3; ++k) dst[3 * (size_t)q + k] = dp[3 * (size_t)q + k];
+    }
+    for (uint32_t qq = 0; qq < d.Q; ++qq) for (int k = 0; k < 3; ++k) dst[3 * (size_t)h->plan.promoted_ids[qq] + k] = red[F6 + 3 * qq + k];
+    return 0;
+  };
+  if (int rc = put_points(out->delta_points, d.dP, dr)) return rc;
+  if (int rc = put_points(out->lambda_points, d.lamP, lr)) return rc;
   return 0;
 }
 
