@@ -311,6 +311,32 @@ RESECT_PROTOTYPES = {
     "lifcal_resect_frames": (C.c_int, [C.POINTER(ResectProblem), C.POINTER(Options), C.c_double, C.c_void_p, dptr]),
 }
 
+
+class IntersectProblem(C.Structure):    # include/lifcal_intersect.h lifcal_intersect_problem
+    _fields_ = [("n_obs", C.c_uint32), ("n_frames", C.c_uint32), ("n_points", C.c_uint32), ("reserved", C.c_uint32),
+                ("u", dptr), ("v", dptr), ("mcx", dptr), ("mcy", dptr), ("pt", uptr), ("fr", uptr),
+                ("cam", dptr), ("views", dptr), ("pts", dptr),
+                ("spx", C.c_double), ("spy", C.c_double), ("scale", C.c_double), ("config", C.c_uint32)]
+
+
+class IntersectPoint(C.Structure):      # lifcal_intersect_point: one 144-byte row per point
+    _fields_ = [("initial_cost", C.c_double), ("final_cost", C.c_double), ("final_radius", C.c_double), ("final_gradient_max_norm", C.c_double),
+                ("H", C.c_double * 6), ("g", C.c_double * 3), ("sum_xx", C.c_double), ("sum_yy", C.c_double),
+                ("n_obs", C.c_uint32), ("n_inliers", C.c_uint32),
+                ("iterations", C.c_int32), ("successful_steps", C.c_int32), ("unsuccessful_steps", C.c_int32), ("termination", C.c_int32)]
+
+
+# the same row as a numpy structured dtype (the table of a call is an array of it)
+INTERSECT_POINT_DTYPE = np.dtype([("initial_cost", "<f8"), ("final_cost", "<f8"), ("final_radius", "<f8"), ("final_gradient_max_norm", "<f8"),
+                                  ("H", "<f8", (6,)), ("g", "<f8", (3,)), ("sum_xx", "<f8"), ("sum_yy", "<f8"),
+                                  ("n_obs", "<u4"), ("n_inliers", "<u4"),
+                                  ("iterations", "<i4"), ("successful_steps", "<i4"), ("unsuccessful_steps", "<i4"), ("termination", "<i4")])
+
+# every symbol include/lifcal_intersect.h declares
+INTERSECT_PROTOTYPES = {
+    "lifcal_intersect_points": (C.c_int, [C.POINTER(IntersectProblem), C.POINTER(Options), C.c_double, C.c_void_p, dptr]),
+}
+
 # every symbol include/lifcal_ba.h declares: name -> (restype, argtypes)
 PROTOTYPES = {
     "lifcal_ba_default_options": (None, [C.POINTER(Options)]),
@@ -369,7 +395,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

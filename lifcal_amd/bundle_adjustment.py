@@ -315,6 +315,26 @@ class BundleAdjustment:
         return resectFrames(pr.cam, pr.pts, u, v, mcx, mcy, pt, fr, views0, pr.struct.config, pr.struct.spx, pr.struct.scale, spy=pr.struct.spy,
                             options=options, inlierThreshold=inlierThreshold)
 
+    def intersectPoints(self, pts0=None, observations=None, options: Optional[capi.Options] = None, inlierThreshold: float = 1.0):
+        """Intersect points against the handle's current (device-resident) camera and poses, which stay constant
+        (lifcal_amd.intersection.intersectPoints).  observations: (u, v, mcx, mcy, pt, fr) of the points to intersect, pt counting
+        them from 0 and fr naming the handle's frames, with their start values pts0; None: the problem's own observations (and,
+        without pts0, its current points).  The handle and its parameters are left as they are."""
+        from .intersection import intersectPoints
+        self.download_parameters()
+        pr = self.problem
+        if observations is None:
+            observations = (pr.u, pr.v, pr.mcx, pr.mcy, pr.pt, pr.fr)
+            if pts0 is None:
+                pts0 = pr.pts
+        if pts0 is None:
+            raise LifcalError("intersectPoints: new observations need start points")
+        u, v, mcx, mcy, pt, fr = observations
+        if options is None:
+            options = capi.Options.from_buffer_copy(self.options); options.world_size = 1; options.rank = 0; options.precision = 0
+        return intersectPoints(pr.cam, pr.views, u, v, mcx, mcy, pt, fr, pts0, pr.struct.config, pr.struct.spx, pr.struct.scale, spy=pr.struct.spy,
+                               options=options, inlierThreshold=inlierThreshold)
+
     # -- the benchmarked unit ------------------------------------------------------------------
     def sweep(self, radius: float = 1e4, want_matrices: bool = False):
         """One Jacobian+Schur sweep; returns a namespace with cost, gradient_max_norm, seconds and,

@@ -1587,3 +1587,6 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 
 // batched pose resection of frames against a constant camera and constant points (include/lifcal_resect.h)
 #include "resection.hpp"
+
+// batched intersection of points against a constant camera and constant poses (include/lifcal_intersect.h)
+#include "intersection.hpp"
