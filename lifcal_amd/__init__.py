@@ -10,3 +10,4 @@ from .mla import MicroLensGrid, RawObservations  # noqa: F401
 from .depth import DepthMaps, backProjectPoints, readDepthData, read_png16, depth_is_estimable  # noqa: F401
 from .resection import resectFrames, ResectionResult  # noqa: F401
 from .intersection import intersectPoints, IntersectionResult  # noqa: F401
+from .start import startPoses, startPoints, StartPosesResult, StartPointsResult  # noqa: F401

@@ -337,6 +337,33 @@ INTERSECT_PROTOTYPES = {
     "lifcal_intersect_points": (C.c_int, [C.POINTER(IntersectProblem), C.POINTER(Options), C.c_double, C.c_void_p, dptr]),
 }
 
+class StartFrame(C.Structure):          # include/lifcal_start.h lifcal_start_frame: one 72-byte row per frame
+    _fields_ = [("sum_w", C.c_double), ("align_rms", C.c_double), ("eig", C.c_double * 2), ("sum_xx", C.c_double), ("sum_yy", C.c_double),
+                ("n_obs", C.c_uint32), ("n_inliers", C.c_uint32), ("n_groups", C.c_uint32), ("n_used", C.c_uint32),
+                ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+class StartGroup(C.Structure):          # lifcal_start_group: one 48-byte row per (frame, point) group
+    _fields_ = [("xyz", C.c_double * 3), ("rms_px", C.c_double), ("fr", C.c_uint32), ("pt", C.c_uint32), ("n_obs", C.c_uint32), ("status", C.c_int32)]
+
+
+class StartPoint(C.Structure):          # lifcal_start_point: one 40-byte row per point
+    _fields_ = [("sum_xx", C.c_double), ("sum_yy", C.c_double), ("min_pivot", C.c_double),
+                ("n_obs", C.c_uint32), ("n_inliers", C.c_uint32), ("status", C.c_int32), ("reserved", C.c_int32)]
+
+
+# the same rows as numpy structured dtypes
+START_FRAME_DTYPE = np.dtype([("sum_w", "<f8"), ("align_rms", "<f8"), ("eig", "<f8", (2,)), ("sum_xx", "<f8"), ("sum_yy", "<f8"),
+                              ("n_obs", "<u4"), ("n_inliers", "<u4"), ("n_groups", "<u4"), ("n_used", "<u4"), ("status", "<i4"), ("reserved", "<i4")])
+START_GROUP_DTYPE = np.dtype([("xyz", "<f8", (3,)), ("rms_px", "<f8"), ("fr", "<u4"), ("pt", "<u4"), ("n_obs", "<u4"), ("status", "<i4")])
+START_POINT_DTYPE = np.dtype([("sum_xx", "<f8"), ("sum_yy", "<f8"), ("min_pivot", "<f8"), ("n_obs", "<u4"), ("n_inliers", "<u4"), ("status", "<i4"), ("reserved", "<i4")])
+
+# every symbol include/lifcal_start.h declares
+START_PROTOTYPES = {
+    "lifcal_start_poses": (C.c_int, [C.POINTER(ResectProblem), C.POINTER(Options), C.c_double, C.c_double, C.c_void_p, C.c_void_p, uptr, dptr]),
+    "lifcal_start_points": (C.c_int, [C.POINTER(IntersectProblem), C.POINTER(Options), C.c_double, C.c_void_p, dptr]),
+}
+
 # every symbol include/lifcal_ba.h declares: name -> (restype, argtypes)
 PROTOTYPES = {
     "lifcal_ba_default_options": (None, [C.POINTER(Options)]),
@@ -395,7 +422,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -335,6 +335,45 @@ class BundleAdjustment:
         return intersectPoints(pr.cam, pr.views, u, v, mcx, mcy, pt, fr, pts0, pr.struct.config, pr.struct.spx, pr.struct.scale, spy=pr.struct.spy,
                                options=options, inlierThreshold=inlierThreshold)
 
+    def startPoses(self, observations=None, n_frames=None, options: Optional[capi.Options] = None, gatePx: float = 1.0, inlierThreshold: float = 1.0,
+                   wantGroups: bool = False):
+        """Closed-form start poses against the handle's current (device-resident) camera and points (lifcal_amd.start.startPoses).
+        observations: (u, v, mcx, mcy, pt, fr) of the n_frames frames to localise, fr counting them from 0; None: the problem's own
+        observations and frames.  The result's views are start values for resectFrames.  The handle is left as it is."""
+        from .start import startPoses
+        self.download_parameters()
+        pr = self.problem
+        if observations is None:
+            observations = (pr.u, pr.v, pr.mcx, pr.mcy, pr.pt, pr.fr)
+            if n_frames is None:
+                n_frames = pr.struct.n_frames
+        if n_frames is None:
+            raise LifcalError("startPoses: new observations need their number of frames")
+        u, v, mcx, mcy, pt, fr = observations
+        if options is None:
+            options = capi.Options.from_buffer_copy(self.options); options.world_size = 1; options.rank = 0; options.precision = 0
+        return startPoses(pr.cam, pr.pts, u, v, mcx, mcy, pt, fr, n_frames, pr.struct.config, pr.struct.spx, pr.struct.scale, spy=pr.struct.spy,
+                          options=options, gatePx=gatePx, inlierThreshold=inlierThreshold, wantGroups=wantGroups)
+
+    def startPoints(self, observations=None, n_points=None, options: Optional[capi.Options] = None, inlierThreshold: float = 1.0):
+        """Closed-form start points against the handle's current (device-resident) camera and poses (lifcal_amd.start.startPoints).
+        observations: (u, v, mcx, mcy, pt, fr) of the n_points points to triangulate, pt counting them from 0 and fr naming the
+        handle's frames; None: the problem's own observations and points.  The result's pts are start values for intersectPoints."""
+        from .start import startPoints
+        self.download_parameters()
+        pr = self.problem
+        if observations is None:
+            observations = (pr.u, pr.v, pr.mcx, pr.mcy, pr.pt, pr.fr)
+            if n_points is None:
+                n_points = pr.struct.n_points
+        if n_points is None:
+            raise LifcalError("startPoints: new observations need their number of points")
+        u, v, mcx, mcy, pt, fr = observations
+        if options is None:
+            options = capi.Options.from_buffer_copy(self.options); options.world_size = 1; options.rank = 0; options.precision = 0
+        return startPoints(pr.cam, pr.views, u, v, mcx, mcy, pt, fr, n_points, pr.struct.config, pr.struct.spx, pr.struct.scale, spy=pr.struct.spy,
+                           options=options, inlierThreshold=inlierThreshold)
+
     # -- the benchmarked unit ------------------------------------------------------------------
     def sweep(self, radius: float = 1e4, want_matrices: bool = False):
         """One Jacobian+Schur sweep; returns a namespace with cost, gradient_max_norm, seconds and,

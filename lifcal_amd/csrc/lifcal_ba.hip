@@ -1590,3 +1590,6 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 
 // batched intersection of points against a constant camera and constant poses (include/lifcal_intersect.h)
 #include "intersection.hpp"
+
+// closed-form start values for the two calls above: poses and points from micro-image rays (include/lifcal_start.h)
+#include "start.hpp"
