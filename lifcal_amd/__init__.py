@@ -11,3 +11,4 @@ from .depth import DepthMaps, backProjectPoints, readDepthData, read_png16, dept
 from .resection import resectFrames, ResectionResult  # noqa: F401
 from .intersection import intersectPoints, IntersectionResult  # noqa: F401
 from .start import startPoses, startPoints, StartPosesResult, StartPointsResult  # noqa: F401
+from .register import registerScene, RegisterResult  # noqa: F401

@@ -364,6 +364,50 @@ START_PROTOTYPES = {
     "lifcal_start_points": (C.c_int, [C.POINTER(IntersectProblem), C.POINTER(Options), C.c_double, C.c_void_p, dptr]),
 }
 
+class RegisterProblem(C.Structure):     # include/lifcal_register.h lifcal_register_problem
+    _fields_ = [("n_obs", C.c_uint32), ("n_frames", C.c_uint32), ("n_points", C.c_uint32), ("reserved", C.c_uint32),
+                ("u", dptr), ("v", dptr), ("mcx", dptr), ("mcy", dptr), ("pt", uptr), ("fr", uptr),
+                ("cam", dptr), ("views", dptr), ("pts", dptr),
+                ("spx", C.c_double), ("spy", C.c_double), ("scale", C.c_double), ("config", C.c_uint32)]
+
+
+class RegisterOptions(C.Structure):     # lifcal_register_options
+    _fields_ = [("gate_px", C.c_double), ("inlier_threshold", C.c_double), ("min_shared", C.c_uint32), ("anchor_frame", C.c_int32),
+                ("anchor_view", dptr), ("max_rounds", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+class RegisterFrame(C.Structure):       # lifcal_register_frame: one 64-byte row per frame
+    _fields_ = [("sum_xx", C.c_double), ("sum_yy", C.c_double), ("final_cost", C.c_double),
+                ("n_obs", C.c_uint32), ("n_obs_used", C.c_uint32), ("n_inliers", C.c_uint32), ("n_groups", C.c_uint32), ("n_used", C.c_uint32),
+                ("n_shared", C.c_uint32), ("status", C.c_int32), ("round", C.c_int32), ("iterations", C.c_int32), ("termination", C.c_int32)]
+
+
+class RegisterPoint(C.Structure):       # lifcal_register_point: one 56-byte row per point
+    _fields_ = [("sum_xx", C.c_double), ("sum_yy", C.c_double), ("final_cost", C.c_double),
+                ("n_obs", C.c_uint32), ("n_obs_used", C.c_uint32), ("n_inliers", C.c_uint32), ("n_frames_used", C.c_uint32),
+                ("status", C.c_int32), ("round", C.c_int32), ("iterations", C.c_int32), ("termination", C.c_int32)]
+
+
+class RegisterSummary(C.Structure):     # lifcal_register_summary
+    _fields_ = [("anchor_frame", C.c_int32), ("n_rounds", C.c_uint32), ("n_frames_registered", C.c_uint32), ("n_points_mapped", C.c_uint32),
+                ("n_groups", C.c_uint32), ("n_groups_used", C.c_uint32)]
+
+
+# the same rows as numpy structured dtypes
+REGISTER_FRAME_DTYPE = np.dtype([("sum_xx", "<f8"), ("sum_yy", "<f8"), ("final_cost", "<f8"),
+                                 ("n_obs", "<u4"), ("n_obs_used", "<u4"), ("n_inliers", "<u4"), ("n_groups", "<u4"), ("n_used", "<u4"),
+                                 ("n_shared", "<u4"), ("status", "<i4"), ("round", "<i4"), ("iterations", "<i4"), ("termination", "<i4")])
+REGISTER_POINT_DTYPE = np.dtype([("sum_xx", "<f8"), ("sum_yy", "<f8"), ("final_cost", "<f8"),
+                                 ("n_obs", "<u4"), ("n_obs_used", "<u4"), ("n_inliers", "<u4"), ("n_frames_used", "<u4"),
+                                 ("status", "<i4"), ("round", "<i4"), ("iterations", "<i4"), ("termination", "<i4")])
+
+# every symbol include/lifcal_register.h declares
+REGISTER_PROTOTYPES = {
+    "lifcal_register_default_options": (None, [C.POINTER(RegisterOptions)]),
+    "lifcal_register_scene": (C.c_int, [C.POINTER(RegisterProblem), C.POINTER(Options), C.POINTER(RegisterOptions), C.c_void_p, C.c_void_p,
+                                        C.POINTER(RegisterSummary), dptr]),
+}
+
 # every symbol include/lifcal_ba.h declares: name -> (restype, argtypes)
 PROTOTYPES = {
     "lifcal_ba_default_options": (None, [C.POINTER(Options)]),
@@ -422,7 +466,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -374,6 +374,29 @@ class BundleAdjustment:
         return startPoints(pr.cam, pr.views, u, v, mcx, mcy, pt, fr, n_points, pr.struct.config, pr.struct.spx, pr.struct.scale, spy=pr.struct.spy,
                            options=options, inlierThreshold=inlierThreshold)
 
+    def registerScene(self, observations=None, n_frames=None, n_points=None, options: Optional[capi.Options] = None, gatePx: float = 1.0,
+                      inlierThreshold: float = 1.0, minShared: int = 6, anchorFrame: int = -1, anchorView=None, maxRounds: int = 0):
+        """Poses and points from micro-image rays alone against the handle's current (device-resident) camera
+        (lifcal_amd.register.registerScene).  observations: (u, v, mcx, mcy, pt, fr) of a sequence with n_frames frames and n_points
+        points, both counted from 0; None: the problem's own observations, frames and points.  The handle is left as it is."""
+        from .register import registerScene
+        self.download_parameters()
+        pr = self.problem
+        if observations is None:
+            observations = (pr.u, pr.v, pr.mcx, pr.mcy, pr.pt, pr.fr)
+            if n_frames is None:
+                n_frames = pr.struct.n_frames
+            if n_points is None:
+                n_points = pr.struct.n_points
+        if n_frames is None or n_points is None:
+            raise LifcalError("registerScene: new observations need their numbers of frames and points")
+        u, v, mcx, mcy, pt, fr = observations
+        if options is None:
+            options = capi.Options.from_buffer_copy(self.options); options.world_size = 1; options.rank = 0; options.precision = 0
+        return registerScene(pr.cam, u, v, mcx, mcy, pt, fr, n_frames, n_points, pr.struct.config, pr.struct.spx, pr.struct.scale, spy=pr.struct.spy,
+                             options=options, gatePx=gatePx, inlierThreshold=inlierThreshold, minShared=minShared, anchorFrame=anchorFrame,
+                             anchorView=anchorView, maxRounds=maxRounds)
+
     # -- the benchmarked unit ------------------------------------------------------------------
     def sweep(self, radius: float = 1e4, want_matrices: bool = False):
         """One Jacobian+Schur sweep; returns a namespace with cost, gradient_max_norm, seconds and,

@@ -31,6 +31,10 @@ struct IntersectArgs {
   LmOpts lo;
   double initial_radius, lm_min, lm_max, thr2;
   uint32_t n_points, robust, jacobi;
+  // the MASKED instantiations only (lifcal_register_scene, register.hpp): the points with pmask[p] != 0 are solved, over their
+  // observations in the frames with fstate[fr] == 1 (registered), and report to reg_rows instead of rows
+  const uint32_t *fstate, *pmask;    // [F], [P]
+  lifcal_register_point* reg_rows;   // [P]
 };
 
 __global__ __launch_bounds__(256) void k_intersect_frames(const double* __restrict__ views, uint32_t F, double* __restrict__ ft) {
@@ -54,7 +58,7 @@ LIFCAL_DEV IsObs is_load(const IntersectArgs& a, const double* __restrict__ cu, 
 
 // normal equations of the point P over its observations [b, e), this lane's share: acc[0..5] H (lower, row-major), [6..8] g = J^T r,
 // [9] cost; EPI: no cost, but [10], [11] sums of e_x^2, e_y^2 and [12] the inlier count of the plain errors
-template <int NR, bool TAN, bool ADJ, bool EPI>
+template <int NR, bool TAN, bool ADJ, bool EPI, bool MASKED = false>
 LIFCAL_DEV void is_sweep(const IntersectArgs& a, const CamConsts& c, const double* __restrict__ cu, uint32_t b, uint32_t e, uint32_t lane,
                          double P0, double P1, double P2, double (&acc)[IS_NEPI]) {
 #pragma unroll
@@ -65,6 +69,7 @@ LIFCAL_DEV void is_sweep(const IntersectArgs& a, const CamConsts& c, const doubl
   for (; i < e; i += 64u) {
     const IsObs o = nx;
     nx = is_load(a, cu, min(i + 64u, e - 1));
+    if (MASKED && a.fstate[o.fr] != 1u) continue;
     const double* __restrict__ ft = a.ft + (size_t)o.fr * FRAME_STRIDE;
     double R[12];
 #pragma unroll
@@ -103,7 +108,7 @@ LIFCAL_DEV void is_sweep(const IntersectArgs& a, const CamConsts& c, const doubl
 }
 
 // value-only cost of the point at P, this lane's share (the candidate of a step)
-template <int NR, bool TAN, bool ADJ>
+template <int NR, bool TAN, bool ADJ, bool MASKED = false>
 LIFCAL_DEV double is_cost(const IntersectArgs& a, const CamConsts& c, const double* __restrict__ cu, uint32_t b, uint32_t e, uint32_t lane,
                           double P0, double P1, double P2) {
   double cost = 0.0, lmant = 1.0; int lexp = 0;
@@ -112,6 +117,7 @@ LIFCAL_DEV double is_cost(const IntersectArgs& a, const CamConsts& c, const doub
   for (; i < e; i += 64u) {
     const IsObs o = nx;
     nx = is_load(a, cu, min(i + 64u, e - 1));
+    if (MASKED && a.fstate[o.fr] != 1u) continue;
     const double* __restrict__ ft = a.ft + (size_t)o.fr * FRAME_STRIDE;
     double R[12];
 #pragma unroll
@@ -182,7 +188,7 @@ LIFCAL_DEV bool is_step(const double* H, const double* g, const double* sig, dou
 }
 
 // (three waves per SIMD: the allocation this bound asks for holds without a spill)
-template <int NR, bool TAN, bool ADJ>
+template <int NR, bool TAN, bool ADJ, bool MASKED = false>
 __global__ __launch_bounds__(IS_THREADS, 3) void k_intersect(IntersectArgs a) {
   // The LM state of a wave: its own row, which no other wave touches.  All 64 lanes run the decisions of lm_step.hpp on it and
   // store the same bits to the same words in the same instruction, so a lane reads back what it wrote: the single-thread
@@ -194,6 +200,12 @@ __global__ __launch_bounds__(IS_THREADS, 3) void k_intersect(IntersectArgs a) {
   if (p >= a.n_points) return;
   const uint32_t b = a.off[p], e = a.off[p + 1];
   if (b == e) return;   // no observations: coordinates and (zeroed) row stay as they are
+  if (MASKED) {   // not mapped, or no observation in a registered frame: a no-op that keeps coordinates and row
+    if (!a.pmask[p]) return;
+    double n = 0.0;
+    for (uint32_t i = b + lane; i < e; i += 64u) if (a.fstate[a.fr[i]] == 1u) n += 1.0;
+    if (wave_sum(n) == 0.0) return;
+  }
   const CamConsts& c = a.camc[0];   // (read where used: a copy would sit in some 90 scalar registers for the whole solve)
   double acc[IS_NEPI], H[IS_NH], g[3], sig[3];
   double P0 = a.pts[3 * (size_t)p], P1 = a.pts[3 * (size_t)p + 1], P2 = a.pts[3 * (size_t)p + 2];
@@ -203,7 +215,7 @@ __global__ __launch_bounds__(IS_THREADS, 3) void k_intersect(IntersectArgs a) {
 
   // sweep + fold: afterwards every lane holds the same H, g and cost, and everything below is computed by all lanes alike
   auto sweep = [&]() {
-    is_sweep<NR, TAN, ADJ, false>(a, c, a.cu, b, e, lane, P0, P1, P2, acc);
+    is_sweep<NR, TAN, ADJ, false, MASKED>(a, c, a.cu, b, e, lane, P0, P1, P2, acc);
 #pragma unroll
     for (int k = 0; k < IS_NSWEEP; ++k) acc[k] = wave_sum(acc[k]);
 #pragma unroll
@@ -223,7 +235,7 @@ __global__ __launch_bounds__(IS_THREADS, 3) void k_intersect(IntersectArgs a) {
     const bool ok = is_step(H, g, sig, lm[LM_RADIUS], a.lm_min, a.lm_max, delta, gtd, ddd);
     if (!lm_check_step(lm, gtd, ddd, ok ? 0.0 : 1.0)) continue;   // invalid step: the same system at half the radius (or the solve has ended)
     const double C0 = P0 + delta[0], C1 = P1 + delta[1], C2 = P2 + delta[2];
-    const double cand = wave_sum(is_cost<NR, TAN, ADJ>(a, c, a.cu, b, e, lane, C0, C1, C2));
+    const double cand = wave_sum(is_cost<NR, TAN, ADJ, MASKED>(a, c, a.cu, b, e, lane, C0, C1, C2));
     // |x|^2 over the camera block as stored and the point: the program of the one-point problem (its constant poses are no blocks)
     const double d0 = C0 - P0, d1 = C1 - P1, d2 = C2 - P2;
     double step2 = 0.0, x2 = cam2;
@@ -234,6 +246,16 @@ __global__ __launch_bounds__(IS_THREADS, 3) void k_intersect(IntersectArgs a) {
   }
 
   // epilogue at the final point, parameters as stored (calcReprojectionError's rule: no sign folding, scale through float)
+  if (MASKED) {   // the point and the solve's figures; the error sums of the row are taken once, at the end of the call
+    if (lane == 0) {
+      double* out = a.pts + 3 * (size_t)p;
+      out[0] = P0; out[1] = P1; out[2] = P2;
+      lifcal_register_point* row = a.reg_rows + p;
+      row->final_cost = lm[LM_X_COST]; row->iterations = (int32_t)lm[LM_ITER];
+      row->termination = lm[LM_TERMINATION] != 0.0 ? (int32_t)lm[LM_TERMINATION] : LIFCAL_BA_TERM_MAX_ITERATIONS;
+    }
+    return;
+  }
   const CamConsts& cs = a.camc[1];
   is_sweep<NR, TAN, ADJ, true>(a, cs, a.cu_stats, b, e, lane, P0, P1, P2, acc);
 #pragma unroll
@@ -322,7 +344,7 @@ int intersect_impl(const lifcal_intersect_problem* p, const lifcal_ba_options* o
   if (err == hipSuccess) err = hipMemsetAsync(dev + at_rows, 0, (size_t)P * sizeof(lifcal_intersect_point), stream);
   if (err == hipSuccess) err = hipEventRecord(ev0, stream);
   if (err == hipSuccess) {
-    IntersectArgs a;
+    IntersectArgs a{};   // (the mask fields of the MASKED instantiations stay null)
     a.off = (const uint32_t*)(dev + at_off); a.fr = (const uint32_t*)(dev + at_fr);
     a.u = (const double*)(dev + at_u); a.v = (const double*)(dev + at_v); a.mcx = (const double*)(dev + at_mx); a.mcy = (const double*)(dev + at_my);
     a.cu = (const double*)(dev + at_cu); a.cu_stats = (const double*)(dev + at_cus); a.camc = (const CamConsts*)(dev + at_camc);

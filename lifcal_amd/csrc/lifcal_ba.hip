@@ -1593,3 +1593,6 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 
 // closed-form start values for the two calls above: poses and points from micro-image rays (include/lifcal_start.h)
 #include "start.hpp"
+
+// registration of a scene from micro-image rays alone: the chain of the three calls above on the device (include/lifcal_register.h)
+#include "register.hpp"

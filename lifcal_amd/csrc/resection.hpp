@@ -12,6 +12,7 @@
 // size, which is therefore the same for every call (RS_THREADS), not a tuning choice made per problem.
 #pragma once
 #include "../../include/lifcal_resect.h"
+#include "../../include/lifcal_register.h"
 
 namespace lifcal {
 
@@ -31,6 +32,11 @@ struct ResectArgs {
   LmOpts lo;
   double initial_radius, lm_min, lm_max, thr2;
   uint32_t robust, jacobi;
+  // the MASKED instantiations only (lifcal_register_scene, register.hpp): the frames with fstate[f] == fwant apart from skip_frame
+  // are solved, over their observations of the points with pmask[pt] != 0, and report to reg_rows instead of rows
+  const uint32_t *pmask, *fstate;    // [P], [F]
+  lifcal_register_frame* reg_rows;   // [F]
+  uint32_t fwant, skip_frame;
 };
 
 template <int NR, bool TAN>
@@ -109,7 +115,7 @@ LIFCAL_DEV void rs_fold(double (&acc)[KA], double* red /* LDS [RS_WAVES * K] */,
 
 // normal equations of the pose over the observations [b, e) of the frame whose table is ft: acc[0..20] H (lower, row-major),
 // [21..26] g = J^T r, [27] cost; EPI: no cost, but [28], [29] sums of e_x^2, e_y^2 and [30] the inlier count of the plain errors
-template <int NR, bool TAN, bool ADJ, bool EPI>
+template <int NR, bool TAN, bool ADJ, bool EPI, bool MASKED = false>
 LIFCAL_DEV void rs_sweep(const ResectArgs& a, const CamConsts& c, const double* ft, const double* __restrict__ cu, uint32_t b, uint32_t e,
                          double (&acc)[RS_NEPI]) {
 #pragma unroll
@@ -121,6 +127,7 @@ LIFCAL_DEV void rs_sweep(const ResectArgs& a, const CamConsts& c, const double* 
   for (; i < e; i += blockDim.x) {
     const RsObs o = nx;
     nx = rs_load(a, cu, min(i + blockDim.x, e - 1));
+    if (MASKED && !a.pmask[a.pt[i]]) continue;
     const double Y0 = ft[0] * o.P0 + ft[1] * o.P1 + ft[2] * o.P2, Y1 = ft[3] * o.P0 + ft[4] * o.P1 + ft[5] * o.P2, Y2 = ft[6] * o.P0 + ft[7] * o.P1 + ft[8] * o.P2;
     double r[2], Jq[2][3];
     obs_pose_eval<NR, TAN, ADJ>(c, Y0 + ft[9], Y1 + ft[10], Y2 + ft[11], o.mx, o.my, o.cux, o.cuy, o.u, o.v, r, Jq);
@@ -158,7 +165,7 @@ LIFCAL_DEV void rs_sweep(const ResectArgs& a, const CamConsts& c, const double* 
 }
 
 // value-only cost of the frame at the pose whose table is ft (the candidate of a step)
-template <int NR, bool TAN, bool ADJ>
+template <int NR, bool TAN, bool ADJ, bool MASKED = false>
 LIFCAL_DEV double rs_cost(const ResectArgs& a, const CamConsts& c, const double* ft, const double* __restrict__ cu, uint32_t b, uint32_t e) {
   double cost = 0.0, lmant = 1.0; int lexp = 0;
   uint32_t i = b + threadIdx.x;
@@ -166,6 +173,7 @@ LIFCAL_DEV double rs_cost(const ResectArgs& a, const CamConsts& c, const double*
   for (; i < e; i += blockDim.x) {
     const RsObs o = nx;
     nx = rs_load(a, cu, min(i + blockDim.x, e - 1));
+    if (MASKED && !a.pmask[a.pt[i]]) continue;
     GroupConsts g;
     group_prepare(c, ft[0] * o.P0 + ft[1] * o.P1 + ft[2] * o.P2 + ft[9], ft[3] * o.P0 + ft[4] * o.P1 + ft[5] * o.P2 + ft[10],
                   ft[6] * o.P0 + ft[7] * o.P1 + ft[8] * o.P2 + ft[11], g);
@@ -232,7 +240,7 @@ LIFCAL_DEV bool rs_step(const double* H, const double* g, const double* sig, dou
   return ok;
 }
 
-template <int NR, bool TAN, bool ADJ>
+template <int NR, bool TAN, bool ADJ, bool MASKED = false>
 __global__ __launch_bounds__(RS_THREADS) void k_resect(ResectArgs a) {
   __shared__ double s_ft[FRAME_STRIDE], s_ftc[FRAME_STRIDE], s_x[6], s_xc[6], s_sig[6], s_delta[6], s_lm[LM_N];
   __shared__ double s_acc[RS_NEPI], s_cand[1], s_cam2[1], s_red[RS_WAVES * RS_NEPI];
@@ -240,8 +248,15 @@ __global__ __launch_bounds__(RS_THREADS) void k_resect(ResectArgs a) {
   const uint32_t f = blockIdx.x, tid = threadIdx.x;
   const uint32_t b = a.off[f], e = a.off[f + 1];
   if (b == e) return;   // no observations: pose and (zeroed) row stay as they are
+  if (MASKED && (a.fstate[f] != a.fwant || f == a.skip_frame)) return;
   const CamConsts c = a.camc[0];
   double acc[RS_NEPI];
+  if (MASKED) {   // no observation of a mapped point: a no-op that keeps pose and row
+    acc[0] = 0.0;
+    for (uint32_t i = b + tid; i < e; i += blockDim.x) if (a.pmask[a.pt[i]]) acc[0] += 1.0;
+    rs_fold<1>(acc, s_red, s_cand);
+    if (s_cand[0] == 0.0) return;
+  }
 
   if (tid == 0) {
 #pragma unroll
@@ -253,7 +268,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_resect(ResectArgs a) {
     s_cam2[0] = c2;
   }
   __syncthreads();
-  rs_sweep<NR, TAN, ADJ, false>(a, c, s_ft, a.cu, b, e, acc);
+  rs_sweep<NR, TAN, ADJ, false, MASKED>(a, c, s_ft, a.cu, b, e, acc);
   rs_fold<RS_NSWEEP>(acc, s_red, s_acc);
   if (tid == 0) {
     double gmax = 0.0;
@@ -288,7 +303,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_resect(ResectArgs a) {
     int st = s_state;
     if (st == RS_STOP) break;
     if (st == RS_CANDIDATE) {
-      acc[0] = rs_cost<NR, TAN, ADJ>(a, c, s_ftc, a.cu, b, e);
+      acc[0] = rs_cost<NR, TAN, ADJ, MASKED>(a, c, s_ftc, a.cu, b, e);
       rs_fold<1>(acc, s_red, s_cand);
       if (tid == 0) {
         double step2 = 0.0, x2 = s_cam2[0];   // |x|^2 over the camera block as stored and the pose: the program of the one-frame problem
@@ -312,7 +327,7 @@ __global__ __launch_bounds__(RS_THREADS) void k_resect(ResectArgs a) {
       st = s_state;
       if (st == RS_STOP) break;
       if (st == RS_COMMIT) {
-        rs_sweep<NR, TAN, ADJ, false>(a, c, s_ft, a.cu, b, e, acc);
+        rs_sweep<NR, TAN, ADJ, false, MASKED>(a, c, s_ft, a.cu, b, e, acc);
         rs_fold<RS_NSWEEP>(acc, s_red, s_acc);
         if (tid == 0) {
           double gmax = 0.0;
@@ -327,6 +342,15 @@ __global__ __launch_bounds__(RS_THREADS) void k_resect(ResectArgs a) {
 
   // epilogue at the final pose, parameters as stored (calcReprojectionError's rule: no sign folding, scale through float)
   __syncthreads();
+  if (MASKED) {   // the pose and the solve's figures; the error sums of the row are taken once, at the end of the call
+    if (tid < 6) a.views[6 * (size_t)f + tid] = s_x[tid];
+    if (tid == 0) {
+      lifcal_register_frame* row = a.reg_rows + f;
+      row->final_cost = s_lm[LM_X_COST]; row->iterations = (int32_t)s_lm[LM_ITER];
+      row->termination = s_lm[LM_TERMINATION] != 0.0 ? (int32_t)s_lm[LM_TERMINATION] : LIFCAL_BA_TERM_MAX_ITERATIONS;
+    }
+    return;
+  }
   const CamConsts cs = a.camc[1];
   rs_sweep<NR, TAN, ADJ, true>(a, cs, s_ft, a.cu_stats, b, e, acc);
   rs_fold<RS_NEPI>(acc, s_red, s_acc);
@@ -414,7 +438,7 @@ int resect_impl(const lifcal_resect_problem* p, const lifcal_ba_options* o, doub
   if (err == hipSuccess) err = hipMemsetAsync(dev + at_rows, 0, (size_t)F * sizeof(lifcal_resect_frame), stream);
   if (err == hipSuccess) err = hipEventRecord(ev0, stream);
   if (err == hipSuccess) {
-    ResectArgs a;
+    ResectArgs a{};   // (the mask fields of the MASKED instantiations stay null)
     a.off = (const uint32_t*)(dev + at_off); a.pt = (const uint32_t*)(dev + at_pt);
     a.u = (const double*)(dev + at_u); a.v = (const double*)(dev + at_v); a.mcx = (const double*)(dev + at_mx); a.mcy = (const double*)(dev + at_my);
     a.cu = (const double*)(dev + at_cu); a.cu_stats = (const double*)(dev + at_cus); a.camc = (const CamConsts*)(dev + at_camc);

@@ -218,6 +218,46 @@ LIFCAL_DEV int start_pose(const double* M, const double* Pm, const double* cm, d
   return LIFCAL_START_FRAME_OK;
 }
 
+// The two sums of the alignment over the groups [gb, ge), this thread's share in ascending position.  MASKED (k_reg_frontier,
+// register.hpp): only the groups whose point has pmask[pt] != 0 take part.
+//   centroids  acc[0] sum w, [1..3] sum w P, [4..6] sum w p_c, [7] the number of groups that take part; w = 1 / Z_c^2
+//   moment     acc[3 i + j] = sum w (P - Pm)_i (p_c - cm)_j
+template <bool MASKED>
+LIFCAL_DEV void st_centroid_sums(const lifcal_start_group* groups, uint32_t gb, uint32_t ge, const double* pts, const uint32_t* pmask, double (&acc)[9]) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+  for (uint32_t g = gb + threadIdx.x; g < ge; g += ST_THREADS) {
+    const lifcal_start_group* r = groups + g;
+    if (r->status == LIFCAL_START_GROUP_USED && (!MASKED || pmask[r->pt])) {
+      const double* P = pts + 3 * (size_t)r->pt;
+      const double w = 1.0 / (r->xyz[2] * r->xyz[2]);
+      acc[0] += w; acc[7] += 1.0;
+#pragma unroll
+      for (int k = 0; k < 3; ++k) { acc[1 + k] += w * P[k]; acc[4 + k] += w * r->xyz[k]; }
+    }
+  }
+}
+
+template <bool MASKED>
+LIFCAL_DEV void st_moment_sums(const lifcal_start_group* groups, uint32_t gb, uint32_t ge, const double* pts, const uint32_t* pmask,
+                               const double (&Pm)[3], const double (&cm)[3], double (&acc)[9]) {
+#pragma unroll
+  for (int k = 0; k < 9; ++k) acc[k] = 0.0;
+  for (uint32_t g = gb + threadIdx.x; g < ge; g += ST_THREADS) {
+    const lifcal_start_group* r = groups + g;
+    if (r->status == LIFCAL_START_GROUP_USED && (!MASKED || pmask[r->pt])) {
+      const double* P = pts + 3 * (size_t)r->pt;
+      const double w = 1.0 / (r->xyz[2] * r->xyz[2]);
+#pragma unroll
+      for (int i = 0; i < 3; ++i) {
+        const double wl = w * (P[i] - Pm[i]);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) acc[3 * i + j] += wl * (r->xyz[j] - cm[j]);
+      }
+    }
+  }
+}
+
 struct StartAlignArgs {
   const uint32_t *off, *fgoff;        // [F + 1] CSR of the observations | of the groups by frame
   const uint32_t* pt;                 // [N] sorted like u .. mcy
@@ -242,18 +282,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_start_align(StartAlignArgs a) {
   double acc[9];
 
   // pass 1: weights, weighted centroids of the world points and of the camera-frame points, the count of used groups
-#pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = 0.0;
-  for (uint32_t g = gb + tid; g < ge; g += ST_THREADS) {
-    const lifcal_start_group* r = a.groups + g;
-    if (r->status == LIFCAL_START_GROUP_USED) {
-      const double* P = a.pts + 3 * (size_t)r->pt;
-      const double w = 1.0 / (r->xyz[2] * r->xyz[2]);
-      acc[0] += w; acc[7] += 1.0;
-#pragma unroll
-      for (int k = 0; k < 3; ++k) { acc[1 + k] += w * P[k]; acc[4 + k] += w * r->xyz[k]; }
-    }
-  }
+  st_centroid_sums<false>(a.groups, gb, ge, a.pts, nullptr, acc);
   rs_fold<8>(acc, s_red, s_out);
   const double sw = s_out[0];
   const uint32_t n_used = (uint32_t)s_out[7];
@@ -266,21 +295,7 @@ __global__ __launch_bounds__(ST_THREADS) void k_start_align(StartAlignArgs a) {
   for (int k = 0; k < 3; ++k) { Pm[k] = s_out[1 + k] / sw; cm[k] = s_out[4 + k] / sw; }
 
   // pass 2: the centred moment M = sum w (P - Pm)(p_c - cm)^T
-#pragma unroll
-  for (int k = 0; k < 9; ++k) acc[k] = 0.0;
-  for (uint32_t g = gb + tid; g < ge; g += ST_THREADS) {
-    const lifcal_start_group* r = a.groups + g;
-    if (r->status == LIFCAL_START_GROUP_USED) {
-      const double* P = a.pts + 3 * (size_t)r->pt;
-      const double w = 1.0 / (r->xyz[2] * r->xyz[2]);
-#pragma unroll
-      for (int i = 0; i < 3; ++i) {
-        const double wl = w * (P[i] - Pm[i]);
-#pragma unroll
-        for (int j = 0; j < 3; ++j) acc[3 * i + j] += wl * (r->xyz[j] - cm[j]);
-      }
-    }
-  }
+  st_moment_sums<false>(a.groups, gb, ge, a.pts, nullptr, Pm, cm, acc);
   rs_fold<9>(acc, s_red, s_out);
   if (tid == 0) {
     double view[6];
