@@ -32,6 +32,12 @@ namespace lifcal {
 constexpr uint32_t DET_NF_MAX = 20;   // widest frame window of a block (Plan::NF_MAX; lifcal_ba.hip checks the two against each other)
 constexpr int SCAL_COST = 0, SCAL_BAD_U = 1, SCAL_GMAX0 = 2, SCAL_N = 2 + 64;
 // host-visible scalars of one LM step
+// the words EVERY block of k_sweep3 adds to (camera x camera block, camera entries of hdiag | gB | rhsacc, cost, max |g_p|) are spread
+// over HOT_ROWS rows in front of each copy of the reduced block: block b adds to row b % HOT_ROWS, so a same-address chain of
+// atomics is n_blocks / HOT_ROWS long instead of n_blocks.  A row is HOT_STRIDE doubles (five 128-byte lines):
+// [0, NCC) camera x camera | NC hdiag | NC gB | NC rhsacc | cost | max |g_p| (as bits).  fold_hot_rows adds the rows onto the canonical words.
+constexpr uint32_t HOT_ROWS = 8, HOT_STRIDE = 80, HOT_N = HOT_ROWS * HOT_STRIDE;
+static_assert(NCMAX * (NCMAX + 1) / 2 + 3 * NCMAX + 2 <= HOT_STRIDE && HOT_STRIDE % 16 == 0, "a row holds every hot word and is a whole number of 128-byte lines");
 constexpr int ST_GTD = 0, ST_DDD = 1, ST_STEP2 = 2, ST_X2 = 3, ST_CAND_COST = 4, ST_CHOL_FAIL = 5, ST_GMAX_RED = 6, ST_DIR = 7, ST_N = 8;
 
 // a set of tiles for the value-only kernels (both sweep paths share them)
@@ -86,6 +92,7 @@ struct Dev {
   double* Wpart;                 // 9 per constraint
   // reduced system (one contiguous all-reduced block): Sband | Sarrow | rhsacc | gB | hdiag | scal
   double *Sband, *Sarrow, *rhsacc, *gB, *hdiag, *scal;
+  double* hot;                   // HOT_ROWS x HOT_STRIDE: rows of the words every k_sweep3 block adds to (this copy's; zero-filled with it)
   double *sig_red, *lam_red, *delta_red, *Linv;  // n_red, n_red, n_red, 36F
   double* lm;                    // LM_N doubles: the device-resident trust-region state (k_lm_control), radius first
   double* step;                  // ST_N scalars
@@ -421,6 +428,42 @@ LIFCAL_DEV double finalize_column(const Dev& d, uint32_t t, double radius) {
   *diag = live ? dg + lam : 1.0;
   rhs[t] = live ? -g + ra : 0.0;
   return fabs(g);
+}
+
+// The rows of the hot words (HOT_ROWS above) onto the canonical words, one thread per word (NCC + 3 NC + 2 <= 74 of them do something).
+// Every update here is a plain read-modify-write, not an atomic: the caller is the ONLY writer of these words while it runs — one
+// workgroup of one kernel, launched once per block and behind every kernel that writes the reduced block (k_finalize's workgroup 0,
+// or k_fold_hot).  The thread requests its HOT_ROWS values together and sums them in row order; the canonical word already holds
+// what the other kernels added (k_sweep, k_schur, k_constraints, k_promote_diag), so this ADDS.
+LIFCAL_DEV void fold_hot_rows(const Dev& d, uint32_t w) {
+  const uint32_t NC = d.nc, NCC = NC * (NC + 1) / 2, nw = NCC + 3 * NC + 2;
+  if (w >= nw) return;
+  double v[HOT_ROWS];
+#pragma unroll
+  for (uint32_t r = 0; r < HOT_ROWS; ++r) v[r] = d.hot[r * HOT_STRIDE + w];
+  const uint32_t camrow = 3 * d.Q, camcol = 6 * d.F + 3 * d.Q;
+  if (w == nw - 1) {   // max |g_p|: bit patterns of non-negative doubles, ordered like integers (k_sweep3 writes them with atomicMax)
+    unsigned long long* dst = (unsigned long long*)(d.scal + SCAL_GMAX0 + d.rank);
+    unsigned long long m = *dst;
+#pragma unroll
+    for (uint32_t r = 0; r < HOT_ROWS; ++r) { const unsigned long long x = (unsigned long long)__double_as_longlong(v[r]); m = x > m ? x : m; }
+    *dst = m;
+    return;
+  }
+  double* dst;
+  if (w < NCC) {
+    uint32_t i = 0; while ((i + 1) * (i + 2) / 2 <= w) ++i;
+    dst = d.Sarrow + (size_t)(camrow + i) * d.ld + camcol + (w - i * (i + 1) / 2);
+  } else if (w < NCC + 3 * NC) {
+    const uint32_t q = w - NCC, vec = q / NC;
+    dst = (vec == 0 ? d.hdiag : (vec == 1 ? d.gB : d.rhsacc)) + camcol + q % NC;
+  } else {
+    dst = d.scal + SCAL_COST;
+  }
+  double s = 0.0;
+#pragma unroll
+  for (uint32_t r = 0; r < HOT_ROWS; ++r) s += v[r];
+  *dst += s;
 }
 
 }  // namespace lifcal
@@ -812,10 +855,14 @@ __global__ void k_det_sum(const double* slots, uint32_t n_wg, uint32_t K, double
 // ---------------------------------------------------------------------------------------------
 // finalize: LM diagonal on the reduced system + rhs row; identity on columns that are not solved for
 // ---------------------------------------------------------------------------------------------
-// Workgroups from n_fin on do something else, beside the finalising ones: they zero-fill `zero` (the copy of the reduced block
-// and step scalars that the NEXT sweep accumulates into; nobody reads it any more)
+// Workgroups from n_fin on do something else, beside the finalising ones: they zero-fill `zero` (the hot rows, the copy of the reduced
+// block and the step scalars that the NEXT sweep accumulates into; nobody reads them any more).
+// fold = 1 (a k_sweep3 sweep that no exchange and no k_fold_hot followed): workgroup 0 owns the hot rows AND the camera columns, the
+// only columns whose inputs the fold changes — it folds, one thread per word, and then finalises those columns behind a barrier, while
+// the other finalising workgroups (n_fin counts workgroup 0) take the columns in front of them.  No other kernel and no other
+// workgroup of this one reads a hot word before this kernel ends.
 constexpr uint32_t FIN_ZERO_PER_WG = 256 * 4;   // doubles per zero-filling workgroup the host sizes the grid with
-__global__ void k_finalize(Dev d, double radius, uint32_t n_fin, double* zero, uint32_t n_zero) {
+__global__ void k_finalize(Dev d, double radius, uint32_t n_fin, double* zero, uint32_t n_zero, uint32_t fold) {
   if (blockIdx.x >= n_fin) {   // (the finalising workgroups have the lowest indices: they are dispatched first)
     const uint32_t n_threads = (gridDim.x - n_fin) * blockDim.x, t0 = (blockIdx.x - n_fin) * blockDim.x + threadIdx.x;
     // 16-byte stores from the first 16-byte aligned double on; the (at most two) doubles around them singly
@@ -827,15 +874,27 @@ __global__ void k_finalize(Dev d, double radius, uint32_t n_fin, double* zero, u
     if (t0 == 0 && head + 2 * n2 < n_zero) zero[n_zero - 1] = 0.0;
     return;
   }
-  const uint32_t t = blockIdx.x * blockDim.x + threadIdx.x;
-  if (t == 0) d.lm[LM_T0] = (double)__builtin_amdgcn_s_memrealtime();   // the linear solve starts here (k_lm_control reads the span: no event records in the device loop)
+  const uint32_t A0 = 6 * d.F + 3 * d.Q;   // first camera column
   double g = 0.0;
-  if (t < d.n_red) g = finalize_column(d, t, radius);
+  if (fold && blockIdx.x == 0) {
+    if (threadIdx.x == 0) d.lm[LM_T0] = (double)__builtin_amdgcn_s_memrealtime();   // the linear solve starts here (k_lm_control reads the span: no event records in the device loop)
+    fold_hot_rows(d, threadIdx.x);
+    __syncthreads();
+    if (A0 + threadIdx.x < d.n_red) g = finalize_column(d, A0 + threadIdx.x, radius);
+  } else {
+    const uint32_t t = (blockIdx.x - fold) * blockDim.x + threadIdx.x;
+    if (!fold && t == 0) d.lm[LM_T0] = (double)__builtin_amdgcn_s_memrealtime();
+    if (t < (fold ? A0 : d.n_red)) g = finalize_column(d, t, radius);
+  }
   // max |g| over the reduced block: one atomic per wave (bit pattern of a non-negative double orders like an integer)
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) g = fmax(g, __shfl_xor(g, m, 64));
   if ((threadIdx.x & 63u) == 0) atomicMax((unsigned long long*)(d.step + ST_GMAX_RED), (unsigned long long)__double_as_longlong(g));
 }
+
+// the fold alone, one workgroup: behind the block kernels wherever a mode-0 block is consumed before, or without, k_finalize (the
+// exchange of the partial blocks, the trial sweeps of the line search)
+__global__ __launch_bounds__(256) void k_fold_hot(Dev d) { fold_hot_rows(d, threadIdx.x); }
 
 // ---------------------------------------------------------------------------------------------
 // block-banded + arrow Cholesky, single workgroup (the reduced system is small and latency bound).

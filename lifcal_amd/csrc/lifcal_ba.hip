@@ -109,7 +109,7 @@ struct lifcal_ba_handle {
   std::vector<void*> allocs;
   uint64_t bytes = 0;
   double* red_block = nullptr; size_t red_count = 0;   // the copy of the reduced block Dev points at (bind_block)
-  double* red_blocks[2] = {nullptr, nullptr};          // block | step scalars | candidate partial sums, twice: a sweep fills the copy the previous one left
+  double* red_blocks[2] = {nullptr, nullptr};          // hot rows | block | step scalars | candidate partial sums, twice: a sweep fills the copy the previous one left
   SweepState ss;                 // which parameters the table sets belong to, which copy of the block is zero (sweep_state.hpp)
   size_t v2_lds_bytes = 0;
   bool use_sweep3 = true;        // wave-specialised LDS-window kernel (LIFCAL_SWEEP_KERNEL=2 selects k_sweep2)
@@ -188,9 +188,13 @@ int do_allreduce(lifcal_ba_handle* h, double* buf, size_t count) {
   return LIFCAL_BA_ERR_COMM;
 }
 
+// does a sweep of this handle exchange its partial reduced block?  (LIFCAL_FORCE_EXCHANGE: run pack / all-gather / unpack at world
+// size 1, for tests.)  launch_sweep decides with the same answer who folds the hot rows: k_fold_hot in front of the exchange, or k_finalize
+bool exchanges(const lifcal_ba_handle* h) { return h->opt.world_size > 1 || h->force_exchange; }
+
 // sum of the per-rank partial reduced blocks: slab all-gather + local add where it applies, else one sum all-reduce
 int exchange_reduced(lifcal_ba_handle* h) {
-  if (h->opt.world_size <= 1 && !h->force_exchange) return 0;   // (LIFCAL_FORCE_EXCHANGE: run pack / all-gather / unpack at world size 1, for tests)
+  if (!exchanges(h)) return 0;
   const bool have_gather = h->ghook ? (h->hook != nullptr) : (h->hook == nullptr && h->comm != nullptr);
   if (!h->xch_ok || !have_gather) return do_allreduce(h, h->red_block, h->red_count);
   const Xch& x = h->xch;
@@ -285,7 +289,7 @@ int build_stats_tables(lifcal_ba_handle* h) {
 void bind_block(lifcal_ba_handle* h, int which) {
   Dev& d = h->d;
   const size_t n_band = (size_t)d.F * (d.bw + 1) * 36, n_arrow = (size_t)(d.NA + 1) * d.ld;
-  h->red_block = h->red_blocks[which];
+  d.hot = h->red_blocks[which]; h->red_block = d.hot + HOT_N;   // (the rows are in front of the block: zero-filled with it, outside what is all-reduced)
   d.Sband = h->red_block; d.Sarrow = d.Sband + n_band; d.rhsacc = d.Sarrow + n_arrow; d.gB = d.rhsacc + d.n_red; d.hdiag = d.gB + d.n_red; d.scal = d.hdiag + d.n_red;
   d.step = d.scal + SCAL_N; h->partial = d.step + ST_N;   // (behind the all-reduced block, not part of it)
 }
@@ -294,7 +298,7 @@ void bind_block(lifcal_ba_handle* h, int which) {
 int acquire_block(lifcal_ba_handle* h) {
   const bool fill = ss_acquire_block(&h->ss);
   bind_block(h, h->ss.bound);
-  if (fill) HIP_TRY(hipMemsetAsync(h->red_block, 0, (h->red_count + ST_N) * sizeof(double), h->stream));
+  if (fill) HIP_TRY(hipMemsetAsync(h->d.hot, 0, (HOT_N + h->red_count + ST_N) * sizeof(double), h->stream));
   return 0;
 }
 
@@ -316,6 +320,18 @@ int launch_value_cost(lifcal_ba_handle* h, const CamConsts* camc, const double* 
     if (d.deterministic) hipLaunchKernelGGL(k_det_sum, dim3(1), dim3(64), 0, h->stream, (const double*)d.det_slots, grid, 1u, out);
   }
   launch_constraints(h, 1, pts, out);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// k_sweep3 (every instantiation) leaves the words all its blocks add to in the copy's hot rows (kernels.hpp: HOT_ROWS) unless the sums
+// are ordered: a mode-0 block of such a handle needs fold_hot_rows before anybody reads those words
+bool uses_hot_rows(const lifcal_ba_handle* h) {
+  return h->d.n_blocks && !h->d.deterministic && !h->use_sweep4 && (h->opt.precision == 1 || h->use_sweep3);
+}
+int launch_fold_hot(lifcal_ba_handle* h) {
+  if (!uses_hot_rows(h)) return 0;
+  hipLaunchKernelGGL(k_fold_hot, dim3(1), dim3(256), 0, h->stream, h->d);
   HIP_TRY(hipGetLastError());
   return 0;
 }
@@ -400,10 +416,12 @@ int launch_sweep(lifcal_ba_handle* h, double radius) {
   if (int rc = launch_blocks(h, radius, 0)) return rc;
   if (d.use_points && d.n_special) hipLaunchKernelGGL(k_schur, dim3((d.n_special + 3) / 4), dim3(256), 0, h->stream, d, radius);
   HIP_TRY(hipGetLastError());
+  const bool exchanged = exchanges(h);
   {
     // multi-rank: the exchange of the partial reduced blocks, bracketed by two records when profiling (world > 1 only: a record is
     // a barrier packet, and a single-rank sweep has no exchange to time)
-    const bool prof_x = h->prof_active() && (h->opt.world_size > 1 || h->force_exchange);
+    const bool prof_x = h->prof_active() && exchanged;
+    if (exchanged) { if (int rc = launch_fold_hot(h)) return rc; }   // the exchange reads the canonical words
     if (prof_x) HIP_TRY(hipEventRecord(h->prof_ev(3), h->stream));
     if (int rc = exchange_reduced(h)) return rc;
     if (prof_x) HIP_TRY(hipEventRecord(h->prof_ev(4), h->stream));
@@ -411,10 +429,12 @@ int launch_sweep(lifcal_ba_handle* h, double radius) {
   {
     // extra workgroups, beside the finalising ones, zero-fill the OTHER copy of the block (and its step scalars) for the next sweep:
     // its last readers were the consumers of the previous sweep, all in front of this one on the stream
-    const uint32_t n_fin = (d.n_red + 255) / 256;
-    const uint32_t n_zero = (uint32_t)(h->red_count + ST_N);
+    // No exchange in front of it: k_finalize folds the hot rows itself, in one workgroup more that also takes the camera columns
+    const uint32_t fold = !exchanged && uses_hot_rows(h) ? 1u : 0u;
+    const uint32_t n_fin = (fold ? (d.n_red - d.nc + 255) / 256 + 1 : (d.n_red + 255) / 256);
+    const uint32_t n_zero = (uint32_t)(HOT_N + h->red_count + ST_N);
     const uint32_t n_fill = std::min((n_zero + FIN_ZERO_PER_WG - 1) / FIN_ZERO_PER_WG, 1024u);
-    hipLaunchKernelGGL(k_finalize, dim3(n_fin + n_fill), dim3(256), 0, h->stream, d, radius, n_fin, h->red_blocks[h->ss.bound ^ 1], n_zero);
+    hipLaunchKernelGGL(k_finalize, dim3(n_fin + n_fill), dim3(256), 0, h->stream, d, radius, n_fin, h->red_blocks[h->ss.bound ^ 1], n_zero, fold);
     HIP_TRY(hipGetLastError());
     ss_finalize_cleaned_other(&h->ss);
   }
@@ -534,6 +554,7 @@ int eval_trial(lifcal_ba_handle* h, double t, double radius, LsSample* smp) {
   int rc = ensure_current_tables(h);   // (at the trial point: the record sees the swap)
   if (!rc) rc = launch_blocks(h, radius, 0);
   if (!rc && d.use_points && d.n_special) { hipLaunchKernelGGL(k_schur, dim3((d.n_special + 3) / 4), dim3(256), 0, h->stream, d, radius); }
+  if (!rc) rc = launch_fold_hot(h);   // (no k_finalize behind a trial sweep)
   if (!rc) rc = do_allreduce(h, h->red_block, h->red_count);
   if (!rc) {
     const uint32_t n = std::max(d.n_red, d.n_owned);
@@ -1052,7 +1073,7 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
   const size_t n_band = (size_t)d.F * (d.bw + 1) * 36, n_arrow = (size_t)(d.NA + 1) * d.ld;
   h->red_count = n_band + n_arrow + 3 * (size_t)d.n_red + SCAL_N;
   // ... | scal | step scalars | candidate partial sums: the host reads each pair with ONE copy.  Two copies, see acquire_block
-  A(h->red_blocks[0], h->red_count + ST_N + 8); A(h->red_blocks[1], h->red_count + ST_N + 8);
+  A(h->red_blocks[0], HOT_N + h->red_count + ST_N + 8); A(h->red_blocks[1], HOT_N + h->red_count + ST_N + 8);
   ss_reset(&h->ss);
   bind_block(h, h->ss.bound);
   A(d.sig_red, d.n_red); A(d.lam_red, d.n_red); A(d.delta_red, d.n_red); A(d.Linv, (size_t)d.F * 36 + 36);

@@ -779,24 +779,28 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
   lds_barrier();
   STAMP(10);
   // The words EVERY block adds to — camera x camera block, camera entries of the three vectors, the scalars — are final here
-  // (the fold below touches pose entries only) and go out first: their device-scope atomics queue up behind those of all other
+  // (the fold below touches pose entries only) and go out first: their device-scope atomics queue up behind those of the other
   // blocks, which finish within a few percent of each other, and that chain then runs under the fold and the issue of the block's
   // own entries instead of behind them (profiles/sweep_tail: 6.0 of the flush's 8.6 us per step belong to these ~75 words).
+  // They go to row b % HOT_ROWS of the copy's hot rows, not to the canonical words (kernels.hpp: HOT_ROWS; chains of n_blocks /
+  // HOT_ROWS atomics instead of n_blocks); fold_hot_rows adds the rows up where the block is consumed.  The diagonal-only pass
+  // (mode 1, once per handle) has no fold behind it and stays on the canonical hdiag words, as does the bad-U count.
   if (!det) {
-    const uint32_t F6 = 6 * d.F, camrow = 3 * d.Q, camcol = F6 + 3 * d.Q;
-    if (mode == 0 && tid < (uint32_t)NCC) {
-      uint32_t i = 0; while ((i + 1) * (i + 2) / 2 <= tid) ++i;
-      const uint32_t j = tid - i * (i + 1) / 2;
-      atomicAdd(d.Sarrow + (size_t)(camrow + i) * d.ld + camcol + j, Scc[tid]);
-    }
-    if (tid < (uint32_t)NC) {
-      atomicAdd(d.hdiag + camcol + tid, vhd[6 * NFm + tid]);
-      if (mode == 0) { atomicAdd(d.gB + camcol + tid, vgB[6 * NFm + tid]); atomicAdd(d.rhsacc + camcol + tid, vrhs[6 * NFm + tid]); }
-    }
-    if (mode == 0 && tid == 0) {
-      atomicAdd(d.scal + SCAL_COST, misc[0]);
-      if (misc[1] != 0.0) atomicAdd(d.scal + SCAL_BAD_U, misc[1]);
-      atomicMax((unsigned long long*)(d.scal + SCAL_GMAX0 + d.rank), *(unsigned long long*)(misc + 2));
+    if (mode == 0) {
+      double* hr = d.hot + (size_t)(b % HOT_ROWS) * HOT_STRIDE;
+      if (tid < (uint32_t)NCC) atomicAdd(hr + tid, Scc[tid]);
+      if (tid < (uint32_t)NC) {
+        atomicAdd(hr + NCC + tid, vhd[6 * NFm + tid]);
+        atomicAdd(hr + NCC + NC + tid, vgB[6 * NFm + tid]);
+        atomicAdd(hr + NCC + 2 * NC + tid, vrhs[6 * NFm + tid]);
+      }
+      if (tid == 0) {
+        atomicAdd(hr + NCC + 3 * NC, misc[0]);
+        if (misc[1] != 0.0) atomicAdd(d.scal + SCAL_BAD_U, misc[1]);
+        atomicMax((unsigned long long*)(hr + NCC + 3 * NC + 1), *(unsigned long long*)(misc + 2));
+      }
+    } else if (tid < (uint32_t)NC) {
+      atomicAdd(d.hdiag + 6 * d.F + 3 * d.Q + tid, vhd[6 * NFm + tid]);
     }
   }
   for (uint32_t i = tid; i < FRV * nf; i += NT) {
@@ -825,7 +829,7 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
     if (tid < 3) out[lay.off_fr + tid] = misc[tid];
     return;
   }
-  const uint32_t F6 = 6 * d.F, camrow = 3 * d.Q, camcol = F6 + 3 * d.Q;
+  const uint32_t camrow = 3 * d.Q;
   // the block's own entries (the words every block adds to went out in front of the fold): vectors, camera x pose rows, then the band
   for (uint32_t i = tid; i < 6 * nf; i += NT) atomicAdd(d.hdiag + 6 * flo + i, vhd[i]);
   if (mode == 0) {
