@@ -5,7 +5,7 @@ the host mirror of the reference entry points and the synthetic scene generator.
 """
 from . import _capi, scene  # noqa: F401
 from .bundle_adjustment import (BundleAdjustment, Covariance, LifcalError, make_config, plan, plan_stats, comm_unique_id, initPlenopticParameters,  # noqa: F401
-                                performBundleAdjustmentWindowed, GroupTable, ResidualReport, sensor_cells)
+                                performBundleAdjustmentWindowed, GroupTable, ResidualReport, sensor_cells, check_priors, prior_from_covariance)
 from .mla import MicroLensGrid, RawObservations  # noqa: F401
 from .depth import DepthMaps, backProjectPoints, readDepthData, read_png16, depth_is_estimable  # noqa: F401
 from .resection import resectFrames, ResectionResult  # noqa: F401

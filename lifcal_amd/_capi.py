@@ -408,6 +408,44 @@ REGISTER_PROTOTYPES = {
                                         C.POINTER(RegisterSummary), dptr]),
 }
 
+class Priors(C.Structure):              # include/lifcal_prior.h lifcal_ba_priors
+    _fields_ = [("cam_mean", dptr), ("cam_info", dptr), ("n_pose_priors", C.c_uint32), ("reserved", C.c_uint32),
+                ("pose_frame", uptr), ("pose_mean", dptr), ("pose_info", dptr)]
+
+
+# every symbol include/lifcal_prior.h declares
+PRIOR_PROTOTYPES = {
+    "lifcal_ba_check_priors": (C.c_int, [C.c_uint32, C.POINTER(Priors)]),
+    "lifcal_ba_set_priors": (C.c_int, [C.c_void_p, C.POINTER(Priors)]),
+    "lifcal_ba_prior_cost": (C.c_int, [C.c_void_p, dptr, dptr]),
+    "lifcal_prior_from_covariance": (C.c_int, [dptr, C.c_uint32, C.c_uint64, C.c_double, dptr, uptr]),
+}
+
+
+class PriorArrays:
+    """Owns contiguous copies of the arrays of a lifcal_ba_priors and the ctypes struct that points into them.
+    camera = (mean[17], info[17, 17]) or None; poses = (frames[n], means[n, 6], infos[n, 6, 6]) or None."""
+
+    def __init__(self, camera=None, poses=None):
+        f8 = lambda a: np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1)).copy()
+        p = Priors()
+        self.cam_mean = self.cam_info = self.pose_frame = self.pose_mean = self.pose_info = None
+        if camera is not None:
+            self.cam_mean, self.cam_info = f8(camera[0]), f8(camera[1])
+            if self.cam_mean.shape[0] != 17 or self.cam_info.shape[0] != 17 * 17:
+                raise ValueError("camera prior: mean[17] and info[17, 17]")
+            p.cam_mean, p.cam_info = as_dptr(self.cam_mean), as_dptr(self.cam_info)
+        if poses is not None:
+            self.pose_frame = np.ascontiguousarray(np.asarray(poses[0], dtype=np.uint32).reshape(-1)).copy()
+            self.pose_mean, self.pose_info = f8(poses[1]), f8(poses[2])
+            n = self.pose_frame.shape[0]
+            if self.pose_mean.shape[0] != 6 * n or self.pose_info.shape[0] != 36 * n:
+                raise ValueError("pose priors: frames[n], means[n, 6] and infos[n, 6, 6]")
+            p.n_pose_priors = n
+            p.pose_frame, p.pose_mean, p.pose_info = as_uptr(self.pose_frame), as_dptr(self.pose_mean), as_dptr(self.pose_info)
+        self.struct = p
+
+
 # every symbol include/lifcal_ba.h declares: name -> (restype, argtypes)
 PROTOTYPES = {
     "lifcal_ba_default_options": (None, [C.POINTER(Options)]),
@@ -466,7 +504,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

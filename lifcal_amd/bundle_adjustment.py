@@ -72,6 +72,35 @@ class Covariance:
     seconds: float = 0.0
     cost: float = 0.0
 
+    def camera_information(self, rcond: float = 1e-9):
+        """(info[17, 17], rank): the camera block as the information matrix of a prior (BundleAdjustment.set_priors(camera=(mean,
+        info))): the pseudo-inverse over the estimable slots, zero rows and columns elsewhere (prior_from_covariance)."""
+        mask = sum(1 << j for j in range(17) if self.estimable[j])
+        return prior_from_covariance(self.camera, mask, rcond)
+
+
+def check_priors(n_frames: int, camera=None, poses=None):
+    """Host-only check of a set of priors (lifcal_ba_check_priors): raises LifcalError with .code LIFCAL_BA_ERR_INVALID_ARG (-1)
+    or LIFCAL_BA_ERR_OUT_OF_RANGE (-4); arguments as BundleAdjustment.set_priors."""
+    lib = capi.load_library()
+    arrs = capi.PriorArrays(camera, poses)
+    _check(lib, lib.lifcal_ba_check_priors(int(n_frames), C.byref(arrs.struct)), "lifcal_ba_check_priors")
+
+
+def prior_from_covariance(cov, use_mask: int, rcond: float = 1e-9):
+    """(info, rank): pseudo-inverse of the sub-matrix of the n x n covariance selected by the bits of use_mask, zero rows and
+    columns elsewhere; eigenvalues below rcond * lambda_max of the Jacobi-scaled sub-matrix count as null
+    (lifcal_prior_from_covariance).  Host only."""
+    lib = capi.load_library()
+    a = np.ascontiguousarray(np.asarray(cov, dtype=np.float64))
+    if a.ndim != 2 or a.shape[0] != a.shape[1]:
+        raise LifcalError("prior_from_covariance: a square matrix")
+    info = np.zeros_like(a)
+    rank = np.zeros(1, np.uint32)
+    _check(lib, lib.lifcal_prior_from_covariance(capi.as_dptr(a), a.shape[0], int(use_mask), float(rcond), capi.as_dptr(info), capi.as_uptr(rank)),
+           "lifcal_prior_from_covariance")
+    return info, int(rank[0])
+
 
 class GroupTable:
     """One table of the residual report: `rows` is a structured array of capi.GROUP_STATS_DTYPE (sum_x, sum_y, sum_xx, sum_yy,
@@ -248,6 +277,25 @@ class BundleAdjustment:
             m = np.ascontiguousarray(fixed, np.uint8)
             assert len(m) == self.problem.struct.n_frames
             _check(self.lib, self.lib.lifcal_ba_set_fixed_frames(self._h, m.ctypes.data_as(C.POINTER(C.c_uint8))), "lifcal_ba_set_fixed_frames")
+
+    def set_priors(self, camera=None, poses=None):
+        """Gaussian priors 1/2 (x - mean)^T info (x - mean) for the following sweeps / solves (lifcal_ba_set_priors, include/lifcal_prior.h):
+        camera = (mean[17], info[17, 17]) in the layout of the problem's cam, poses = (frames[n] strictly ascending, means[n, 6],
+        infos[n, 6, 6]).  Replaces the priors the handle had; both None clears them.  Slots that are not free parameters of the
+        handle (fixed_mask, absent distortion slots, constant poses) leave the term."""
+        if camera is None and poses is None:
+            return self.clear_priors()
+        arrs = capi.PriorArrays(camera, poses)
+        _check(self.lib, self.lib.lifcal_ba_set_priors(self._h, C.byref(arrs.struct)), "lifcal_ba_set_priors")
+
+    def clear_priors(self):
+        _check(self.lib, self.lib.lifcal_ba_set_priors(self._h, None), "lifcal_ba_set_priors")
+
+    def prior_cost(self):
+        """(camera, poses): 1/2 d^T info d of the camera prior and summed over the pose priors at the device-resident parameters."""
+        c = np.zeros(2)
+        _check(self.lib, self.lib.lifcal_ba_prior_cost(self._h, capi.as_dptr(c[0:1]), capi.as_dptr(c[1:2])), "lifcal_ba_prior_cost")
+        return float(c[0]), float(c[1])
 
     def covariance(self, gauge_frame: int = -1, want_pose_blocks: bool = True, scale_by_residual_variance: bool = False,
                    null_rcond: Optional[float] = None, estimable_tol: Optional[float] = None, want_pose_band: bool = False) -> Covariance:

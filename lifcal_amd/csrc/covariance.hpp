@@ -457,6 +457,7 @@ extern "C" int lifcal_ba_covariance(lifcal_ba_handle* h, const lifcal_ba_covaria
     if (F) HIP_TRY(hipMemcpy(h->frame_live_dev, live_saved.data(), F, hipMemcpyHostToDevice));
     HIP_TRY(hipMemcpy(d.lm, lm_saved, sizeof(lm_saved), hipMemcpyHostToDevice));
     h->sigma_valid = sigma_saved; h->prof_on = prof_saved;
+    if (gauge >= 0) { h->frame_live_host = live_saved; h->prior_stale = h->has_priors; }   // (a pose prior on the gauge frame comes back)
     return 0;
   };
   auto bail = [&](int rc) { const std::string e = g_last_error; restore(); g_last_error = e; return rc; };
@@ -464,6 +465,7 @@ extern "C" int lifcal_ba_covariance(lifcal_ba_handle* h, const lifcal_ba_covaria
   if (gauge >= 0) {
     std::vector<uint8_t> live(live_saved); live[gauge] = 0;
     if (hipMemcpy(h->frame_live_dev, live.data(), F, hipMemcpyHostToDevice) != hipSuccess) { g_last_error = "lifcal_ba_covariance: frame mask upload failed"; return bail(LIFCAL_BA_ERR_HIP); }
+    h->frame_live_host = live; h->prior_stale = h->has_priors;   // a prior on the gauge frame's pose leaves the term with its columns
   }
   // ---- the undamped reduced system, K1 .. K3 ----
   if (hipEventRecord(h->ev0, h->stream) != hipSuccess) { g_last_error = "hipEventRecord failed"; return bail(LIFCAL_BA_ERR_HIP); }
@@ -515,7 +517,7 @@ extern "C" int lifcal_ba_covariance(lifcal_ba_handle* h, const lifcal_ba_covaria
   n_free += 3 * n_pts;
   uint32_t live_mask = 0;
   for (uint32_t j = 0; j < nc; ++j) if (cc.chm[j] != 0.0) { live_mask |= 1u << j; ++n_free; }
-  const uint64_t m = 2 * (uint64_t)h->plan.n_obs_local + d.M_local;
+  const uint64_t m = 2 * (uint64_t)h->plan.n_obs_local + d.M_local + prior_rows(h, h->frame_live_host);   // (priors: one row per live slot with a non-zero prior row)
   const double r = (double)n_free - (gauge >= 0 ? 6.0 : 0.0) - (double)nulls.size();
   const double sigma2 = (double)m > r ? 2.0 * cost / ((double)m - r) : std::numeric_limits<double>::quiet_NaN();
   const double mult = o.scale_by_residual_variance ? sigma2 : 1.0;

@@ -98,6 +98,11 @@ struct Dev {
   double* step;                  // ST_N scalars
   double* dP;                    // 3P: unscaled point step of the last back-substitution (line search re-applies it)
   unsigned long long* dbg;       // diagnostic build only (LIFCAL_STAMPS): per-block phase cycle counts
+  // Gaussian priors (priors.hpp, k_priors): null / 0 on a handle without them.  Behind every other member: nothing in front moves
+  const double *pr_cam_mean, *pr_cam_info;       // nc, nc x nc (structural columns; rows and columns of slots that are not free are zero), or null
+  const uint32_t* pr_frame;                      // pr_n prior-ed frames, ascending
+  const double *pr_pose_mean, *pr_pose_info;     // 6 pr_n, 36 pr_n (blocks of frames whose pose is not free are zero)
+  uint32_t pr_n;
 };
 
 // trust-region radius of a kernel: the launch argument, or (negative argument) the device-resident state

@@ -22,6 +22,7 @@
 #include <vector>
 
 #include "../../include/lifcal_ba.h"
+#include "../../include/lifcal_prior.h"
 #include "kernels.hpp"
 #include "plan.hpp"
 #include "linesearch.hpp"
@@ -147,6 +148,12 @@ struct lifcal_ba_handle {
   double *res_ex = nullptr, *res_ey = nullptr, *res_w = nullptr;
   uint32_t *res_lens = nullptr, *res_src1 = nullptr, *res_src2 = nullptr, *res_off[3] = {nullptr, nullptr, nullptr}, *res_idx[3] = {nullptr, nullptr, nullptr}, *res_tot_off = nullptr;
   lifcal_ba_group_stats* res_rows = nullptr;
+  // Gaussian priors (priors.hpp): the caller's priors as given (symmetrised, 17 x 17 and 6 x 6 per frame), the device buffer Dev points
+  // into (masked by the live slots: stale when the frame mask changed), its staging copy
+  bool has_priors = false, prior_stale = false;
+  std::vector<double> pr_cam_mean, pr_cam_info, pr_pose_mean, pr_pose_info, pr_stage;
+  std::vector<uint32_t> pr_frame;
+  double* pr_buf = nullptr; uint32_t* pr_frame_dev = nullptr; size_t pr_cap = 0;
   bool trace = false;            // LIFCAL_TRACE=1: one stderr line per host decision of the LM loop, tagged with the rank
   double* Lpanel = nullptr; size_t bandw_lds = 0, backw_lds = 0; bool bandw_ok = false;
   CrPlan cr; bool use_cr = false;   // block odd-even reduction (bandchol3.hpp): long sequences
@@ -161,6 +168,9 @@ struct lifcal_ba_handle {
   bool prof_in_span() const { return prof_on && prof_seen < prof_cap; }
   bool prof_active() const { return prof_in_span() && prof_seen % prof_stride == 0; }
 };
+
+// Gaussian priors on camera and poses: k_priors, launch_priors and the C ABI of include/lifcal_prior.h
+#include "priors.hpp"
 
 namespace {
 
@@ -308,8 +318,9 @@ void launch_constraints(lifcal_ba_handle* h, int cost_only, const double* pts, d
   if (d.M_local) hipLaunchKernelGGL(k_constraints, dim3(d.deterministic ? 1 : (d.M_local + 63) / 64), dim3(d.deterministic ? 1 : 64), 0, h->stream, d, cost_only, pts, out);
 }
 
-// cost of a parameter set (its tables, its points) through the value-only kernel, both tile sets, + the constraint term, added to *out
-int launch_value_cost(lifcal_ba_handle* h, const CamConsts* camc, const double* ft, const double* lt, const double* pts, double* out) {
+// cost of a parameter set (its tables, its points; cam / views: the raw parameters the tables were built from) through the value-only
+// kernel, both tile sets, + the constraint term + the prior term, added to *out
+int launch_value_cost(lifcal_ba_handle* h, const CamConsts* camc, const double* ft, const double* lt, const double* pts, const double* cam, const double* views, double* out) {
   const Dev& d = h->d;
   for (const TileSet* ts : {&h->ts1, &h->ts2}) {
     if (!ts->n_tiles) continue;
@@ -321,7 +332,7 @@ int launch_value_cost(lifcal_ba_handle* h, const CamConsts* camc, const double* 
   }
   launch_constraints(h, 1, pts, out);
   HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_priors(h, 1, cam, views, out);
 }
 
 // k_sweep3 (every instantiation) leaves the words all its blocks add to in the copy's hot rows (kernels.hpp: HOT_ROWS) unless the sums
@@ -388,7 +399,7 @@ int launch_blocks(lifcal_ba_handle* h, double radius, int mode) {
   launch_constraints(h, 0, d.pts, d.scal + SCAL_COST);
   if (d.Q && d.use_points) hipLaunchKernelGGL(k_promote_diag, dim3((d.Q + 63) / 64), dim3(64), 0, h->stream, d);
   HIP_TRY(hipGetLastError());
-  return 0;
+  return launch_priors(h, 0, d.cam, d.views, d.scal + SCAL_COST);   // (both modes: the diagonal of the prior belongs to the Jacobi scaling)
 }
 
 // one Jacobian + Schur sweep at the current point and the given trust-region radius
@@ -498,7 +509,7 @@ int launch_candidate(lifcal_ba_handle* h) {
   HIP_TRY(hipGetLastError());
   ss_candidate_written(&h->ss);
   if (int rc = build_candidate_tables(h)) return rc;
-  if (int rc = launch_value_cost(h, d.camc_c, d.ft_c, d.lt_c, d.use_points ? d.pts_c : d.pts, h->partial + 4)) return rc;
+  if (int rc = launch_value_cost(h, d.camc_c, d.ft_c, d.lt_c, d.use_points ? d.pts_c : d.pts, d.cam_c, d.views_c, h->partial + 4)) return rc;
   return do_allreduce(h, h->partial, 8);
 }
 
@@ -507,7 +518,7 @@ int launch_candidate(lifcal_ba_handle* h) {
 int cost64_current(lifcal_ba_handle* h, double* cost) {
   Dev& d = h->d;
   HIP_TRY(hipMemsetAsync(h->partial, 0, 8 * sizeof(double), h->stream));
-  if (int rc = launch_value_cost(h, d.camc, d.ft, d.lt, d.pts, h->partial + 4)) return rc;
+  if (int rc = launch_value_cost(h, d.camc, d.ft, d.lt, d.pts, d.cam, d.views, h->partial + 4)) return rc;
   if (int rc = do_allreduce(h, h->partial, 8)) return rc;
   HIP_TRY(hipMemcpyAsync(cost, h->partial + 4, sizeof(double), hipMemcpyDeviceToHost, h->stream));
   HIP_TRY(hipStreamSynchronize(h->stream));
@@ -566,7 +577,7 @@ int eval_trial(lifcal_ba_handle* h, double t, double radius, LsSample* smp) {
   // loop come from the fp64 value kernel — near convergence the offset between the two arithmetics (~1e-7 relative) is far larger
   // than the Armijo margin, so the trial value is taken from the SAME fp64 kernel on the trial point's tables (ls_buf[3])
   const bool value64 = h->opt.precision == 1;
-  if (!rc && value64) rc = launch_value_cost(h, d.camc, d.ft, d.lt, d.pts, h->ls_buf + 3);   // (swapped: the trial point)
+  if (!rc && value64) rc = launch_value_cost(h, d.camc, d.ft, d.lt, d.pts, d.cam, d.views, h->ls_buf + 3);   // (swapped: the trial point)
   swap_current_candidate(h);
   if (rc) return rc;
   if (int rc2 = do_allreduce(h, h->ls_buf, value64 ? 4 : 3)) return rc2;
@@ -640,7 +651,7 @@ int line_search(lifcal_ba_handle* h, double x_cost, double g0, double radius, in
   if (int rc = launch_apply_step(h, t_opt)) return rc;
   HIP_TRY(hipMemsetAsync(h->partial, 0, 8 * sizeof(double), h->stream));
   if (int rc = build_candidate_tables(h)) return rc;
-  if (int rc = launch_value_cost(h, d.camc_c, d.ft_c, d.lt_c, d.use_points ? d.pts_c : d.pts, h->partial + 4)) return rc;
+  if (int rc = launch_value_cost(h, d.camc_c, d.ft_c, d.lt_c, d.use_points ? d.pts_c : d.pts, d.cam_c, d.views_c, h->partial + 4)) return rc;
   if (int rc = do_allreduce(h, h->partial, 8)) return rc;
   if (int rc = do_allreduce(h, h->ls_buf, 2)) return rc;
   double hb[8], hp[8];
@@ -1152,6 +1163,8 @@ void lifcal_ba_destroy(lifcal_ba_handle* h) {
   if (h->stream) (void)hipStreamSynchronize(h->stream);
   if (h->comm && !h->comm_borrowed && g_rccl.CommDestroy) g_rccl.CommDestroy(h->comm);
   for (void* p : h->allocs) (void)hipFree(p);
+  if (h->pr_buf) (void)hipFree(h->pr_buf);
+  if (h->pr_frame_dev) (void)hipFree(h->pr_frame_dev);
   if (h->h_scal) (void)hipHostFree(h->h_scal);
   if (h->h_lm) (void)hipHostFree(h->h_lm);
   if (h->ev0) (void)hipEventDestroy(h->ev0);
@@ -1172,6 +1185,7 @@ int lifcal_ba_set_fixed_frames(lifcal_ba_handle* h, const uint8_t* fixed) {
   HIP_TRY(hipStreamSynchronize(h->stream));
   if (!live.empty()) HIP_TRY(hipMemcpy(h->frame_live_dev, live.data(), live.size(), hipMemcpyHostToDevice));
   h->frame_live_host = live;
+  h->prior_stale = h->has_priors;   // pose priors of frames held constant leave the term: the mask is applied again before the next sweep
   h->sigma_valid = false;   // the Jacobi scaling is fixed at the first sweep of a solve: a new column set starts a new solve
   h->swept = false;
   return 0;

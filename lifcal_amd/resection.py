@@ -75,6 +75,10 @@ class ResectionResult:
     def final_cost(self) -> np.ndarray:
         return self.rows["final_cost"]
 
+    def pose_information(self) -> np.ndarray:
+        """(F, 6, 6): H per frame, the information matrix of a pose prior (BundleAdjustment.set_priors(poses=(frames, views, infos)))."""
+        return self.H
+
     def pose_covariance(self) -> np.ndarray:
         """(F, 6, 6): inverse of H per frame (Ceres units: unit-variance pixel residuals).  NaN where H is not positive definite."""
         out = np.full((len(self.rows), 6, 6), np.nan)
