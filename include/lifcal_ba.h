@@ -410,6 +410,21 @@ typedef struct lifcal_ba_plan_statistics {
 } lifcal_ba_plan_statistics;
 int lifcal_ba_plan_stats(const lifcal_ba_problem* p, int32_t rank, int32_t world_size, lifcal_ba_plan_statistics* out);
 
+/* Host-only: the same schedule tile by tile and pass by pass, for tests that need a scene to contain the edge cases of the window
+ * kernels (a wave's observation loop over 0, 1, 2 or an odd number of rows; passes of one point and of the cap; the last tile's
+ * clamped prefetch).  A tile is 64 consecutive lanes of a pass, its steps the rows of the padded observation payload it owns. */
+typedef struct lifcal_ba_plan_shape_figures {
+  uint64_t tiles_0_steps, tiles_1_step, tiles_2_steps, tiles_odd_steps /* odd and >= 3 */, tiles_even_steps /* even and >= 4 */;
+  uint64_t ell_rows;           /* rows of 64 words the padded observation arrays hold (the payload's rows + padding)          */
+  uint64_t max_row_read;       /* highest row any wave reads with its prologue and its clamped prefetch: must be < ell_rows   */
+  uint64_t last_tile_row0;     /* first row of the last tile of the last block                                               */
+  uint32_t last_tile_steps;
+  uint32_t min_pass_points, max_pass_points;    /* points per pass (np): at most 64                                          */
+  uint32_t min_block_passes, max_block_passes;
+  uint32_t reserved;
+} lifcal_ba_plan_shape_figures;
+int lifcal_ba_plan_shape(const lifcal_ba_problem* p, int32_t rank, int32_t world_size, lifcal_ba_plan_shape_figures* out);
+
 /* ---- shard-local problems (multi-GPU without handing every rank the whole observation list) ----
  * lifcal_ba_create takes the WHOLE problem on every rank and keeps the observations of the points the rank owns.  For long
  * sequences (BASELINE configs[3], configs[4]) a launcher can instead partition ONCE from the index arrays alone (pt, fr: 8 bytes

@@ -136,7 +136,14 @@ class PlanStats(C.Structure):     # lifcal_ba_plan_statistics
                 ("block_cost_mean", C.c_double), ("block_cost_max", C.c_double)]
 
 
-ALLREDUCE_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
+class PlanShape(C.Structure):     # lifcal_ba_plan_shape_figures
+    _fields_ = [("tiles_0_steps", C.c_uint64), ("tiles_1_step", C.c_uint64), ("tiles_2_steps", C.c_uint64), ("tiles_odd_steps", C.c_uint64),
+                ("tiles_even_steps", C.c_uint64), ("ell_rows", C.c_uint64), ("max_row_read", C.c_uint64), ("last_tile_row0", C.c_uint64),
+                ("last_tile_steps", C.c_uint32), ("min_pass_points", C.c_uint32), ("max_pass_points", C.c_uint32),
+                ("min_block_passes", C.c_uint32), ("max_block_passes", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+ALLREDUCE_FN =C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 ALLGATHER_FN = C.CFUNCTYPE(C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_size_t, C.c_void_p)
 
 class InitProblem(C.Structure):
@@ -481,6 +488,7 @@ PROTOTYPES = {
     "lifcal_ba_version": (C.c_char_p, []),
     "lifcal_ba_plan": (C.c_int, [C.POINTER(Problem), C.c_int32, C.c_int32, C.POINTER(PlanInfo), uptr, uptr]),
     "lifcal_ba_plan_stats": (C.c_int, [C.POINTER(Problem), C.c_int32, C.c_int32, C.POINTER(PlanStats)]),
+    "lifcal_ba_plan_shape": (C.c_int, [C.POINTER(Problem), C.c_int32, C.c_int32, C.POINTER(PlanShape)]),
     "lifcal_ba_partition_points": (C.c_int, [C.POINTER(Problem), C.POINTER(Partition)]),
     "lifcal_ba_create_shard": (C.c_int, [C.POINTER(Problem), C.POINTER(Partition), C.POINTER(Options), C.POINTER(C.c_void_p)]),
     "lifcal_ba_plan_shard": (C.c_int, [C.POINTER(Problem), C.POINTER(Partition), C.c_int32, C.POINTER(PlanInfo)]),

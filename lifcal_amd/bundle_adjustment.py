@@ -590,3 +590,12 @@ def plan_stats(problem: capi.ProblemArrays, rank: int = 0, world_size: int = 1) 
     st = capi.PlanStats()
     _check(lib, lib.lifcal_ba_plan_stats(C.byref(problem.struct), rank, world_size, C.byref(st)), "lifcal_ba_plan_stats")
     return st
+
+
+def plan_shape(problem: capi.ProblemArrays, rank: int = 0, world_size: int = 1) -> capi.PlanShape:
+    """Host-only: the same schedule tile by tile and pass by pass (tiles by their step count, points per pass, passes per block, the
+    rows the last tile's clamped prefetch reads against the rows the padded arrays hold)."""
+    lib = capi.load_library()
+    sh = capi.PlanShape()
+    _check(lib, lib.lifcal_ba_plan_shape(C.byref(problem.struct), rank, world_size, C.byref(sh)), "lifcal_ba_plan_shape")
+    return sh

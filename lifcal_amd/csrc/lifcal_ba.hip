@@ -894,6 +894,14 @@ int lifcal_ba_plan_stats(const lifcal_ba_problem* p, int32_t rank, int32_t world
   return 0;
 }
 
+int lifcal_ba_plan_shape(const lifcal_ba_problem* p, int32_t rank, int32_t world_size, lifcal_ba_plan_shape_figures* out) {
+  if (!out) return LIFCAL_BA_ERR_INVALID_ARG;
+  Plan pl; PlanChoice c;
+  if (int rc = plan_for_environment(p, rank, world_size, 0, 0, nullptr, &pl, &c)) return rc;
+  plan_shape(pl, out);
+  return 0;
+}
+
 static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, lifcal_ba_handle** out, const lifcal_ba_partition* part);
 
 int lifcal_ba_create(const lifcal_ba_problem* p, const lifcal_ba_options* o, lifcal_ba_handle** out) { return create_impl(p, o, out, nullptr); }

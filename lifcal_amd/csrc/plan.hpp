@@ -979,6 +979,33 @@ inline void plan_stats(const Plan& L, lifcal_ba_plan_statistics* out) {
   *out = s;
 }
 
+// Shape of the v2 schedule, tile by tile and pass by pass (lifcal_ba_plan_shape): what the tests of the window kernels' edge cases
+// (loop prologue and odd tail, clamped prefetch, padded lanes of the factor phase) need to know that a scene contains.
+inline void plan_shape(const Plan& L, lifcal_ba_plan_shape_figures* out) {
+  lifcal_ba_plan_shape_figures s;
+  std::memset(&s, 0, sizeof(s));
+  const uint32_t PT = L.pass_tiles();
+  s.min_pass_points = s.min_block_passes = UINT32_MAX;
+  s.ell_rows = L.v2_lens.size() / 64;
+  for (uint32_t b = 0; b < L.n_blocks; ++b) {
+    const uint32_t n = L.blk_pass0[b + 1] - L.blk_pass0[b];
+    s.min_block_passes = std::min(s.min_block_passes, n); s.max_block_passes = std::max(s.max_block_passes, n);
+  }
+  for (uint32_t ps = 0; ps < L.n_passes; ++ps) {
+    s.min_pass_points = std::min(s.min_pass_points, L.pass_np[ps]); s.max_pass_points = std::max(s.max_pass_points, L.pass_np[ps]);
+    for (uint32_t w = 0; w < PT; ++w) {
+      const uint32_t row0 = L.v2_tile_row0[(size_t)ps * PT + w], r = L.v2_tile_row0[(size_t)ps * PT + w + 1] - row0;
+      if (r == 0) ++s.tiles_0_steps; else if (r == 1) ++s.tiles_1_step; else if (r == 2) ++s.tiles_2_steps; else if (r & 1u) ++s.tiles_odd_steps; else ++s.tiles_even_steps;
+      // the rows a wave reads for its tile: row0 and row0 + (r > 1) in the prologue, row0 + min(k + 2, r - 1) in the loop
+      s.max_row_read = std::max<uint64_t>(s.max_row_read, (uint64_t)row0 + std::max(r, 1u) - 1);
+      if (ps + 1 == L.n_passes && w + 1 == PT) { s.last_tile_steps = r; s.last_tile_row0 = row0; }
+    }
+  }
+  if (L.n_passes == 0) s.min_pass_points = 0;
+  if (L.n_blocks == 0) s.min_block_passes = 0;
+  *out = s;
+}
+
 // the ownership rule of build_plan applied to the index arrays of the whole problem (lifcal_ba_partition_points)
 inline int partition_points(const lifcal_ba_problem* p, lifcal_ba_partition* out) {
   if (!p || !out || out->world_size < 1 || out->world_size > 64 || !out->point_owner || !out->rank_first || !out->rank_frames || !out->rank_obs || !out->frame_used) return LIFCAL_BA_ERR_INVALID_ARG;

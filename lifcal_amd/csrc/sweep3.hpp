@@ -71,11 +71,11 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
 #endif
   // pass descriptors and per-lane slot words, one pass ahead (see k_sweep2)
   const uint32_t ps_begin = d.blk_pass0[b], ps_end = d.blk_pass0[b + 1];
-  uint32_t nx_np = 0, nx_gid0 = 0, nx_si = 0, nx_pt = 0, nx_fp = 0, nx_gid = 0, nx_r[2] = {0, 0};
+  uint32_t nx_np = 0, nx_si = 0, nx_pt = 0, nx_fp = 0, nx_gid = 0, nx_r[2] = {0, 0};
   uint32_t vz;
   asm volatile("v_mov_b32 %0, 0" : "=v"(vz));
   auto fetch_pass = [&](uint32_t q) {
-    nx_np = d.pass_np[q + vz]; nx_gid0 = d.pass_gid0[q + vz];
+    nx_np = d.pass_np[q + vz];
     nx_si = d.v2_slot[(size_t)q * LP + t256]; nx_pt = d.v2f_pt[(size_t)q * LP + t256]; nx_gid = d.v2_gidx[(size_t)q * LP + t256];
     nx_r[0] = d.v2_tile_row0[q * WR + wl + vz]; nx_r[1] = d.v2_tile_row0[q * WR + wl + 1 + vz];   // observation rows of the wave's tile
     nx_fp = d.v2_passpt[(size_t)q * 64 + (tid & 63u)];
@@ -273,8 +273,6 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
       const uint32_t np = __builtin_amdgcn_readfirstlane(nx_np);
       const uint32_t si = nx_si, pt = nx_pt, fp = nx_fp, gidx = nx_gid;
       const uint32_t row0 = __builtin_amdgcn_readfirstlane(nx_r[0]), kmax = __builtin_amdgcn_readfirstlane(nx_r[1]) - row0;
-      double fsg0 = 1.0, fsg1 = 1.0, fsg2 = 1.0;
-      if (mode == 0 && tid < np) { fsg0 = d.sigP[3 * (size_t)fp]; fsg1 = d.sigP[3 * (size_t)fp + 1]; fsg2 = d.sigP[3 * (size_t)fp + 2]; }
       if (ps + 1 < ps_end) fetch_pass(ps + 1);
       const uint32_t krows = (3 * np + 7u) & ~7u;   // K of the product: multiple of 8 (two row groups of 4, one per role)
       const uint32_t cnt = si & 0xFFu, lf = (si >> 8) & 0xFFu, lp = (si >> 16) & 0xFFu;
@@ -319,6 +317,12 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
       // All prefetch loads are UNCONDITIONAL (row index clamped; the ELL padding is valid memory): with loads under a lane
       // condition the compiler's wait-count merge degenerates to vmcnt(0) at the top of the evaluation, i.e. the step would
       // wait for the prefetch it has just issued (HBM latency, every step).
+      // What the compiled loop does (profiles/sweep_loads/): the ODD half reaches the row through counted waits (vmcnt 6, 5, 4,
+      // 3: the words of the step after next stay in flight); the header of the EVEN half still waits vmcnt(0), because the
+      // prologue above issues the row of step 0 last and the counts of the entry path and the back edge merge there.  The
+      // prologue in the loop's order (words, row, words) gives counted waits in both halves and MEASURES SLOWER (the row's
+      // address then waits for the lens index in front of barrier P1); the row requested earlier, inside the evaluation,
+      // measures no gain beyond the spread; neither is built.
       // The loop is unrolled by two over two sets of observation words (even / odd steps): a rotating set would make the
       // compiler copy freshly loaded registers at the back-edge, i.e. wait for the loads it has just issued.
       ET Ln[LENS_STRIDE];
@@ -384,12 +388,22 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
       // rotation, rotated point, d(R P)/d(angles): read again here instead of being carried through the loop (42 registers)
       LaneGeom q;
       { uint32_t fr2 = fr, pt2 = pt; asm volatile("" : "+v"(fr2), "+v"(pt2)); lane_geom(fr2, pt2, q); }
-      asm volatile("" :: "v"(nx_si), "v"(nx_pt), "v"(nx_fp), "v"(nx_np), "v"(nx_gid0), "v"(nx_gid), "v"(nx_r[0]), "v"(nx_r[1]));
-      asm volatile("" :: "v"(fsg0), "v"(fsg1), "v"(fsg2));
+      asm volatile("" :: "v"(nx_si), "v"(nx_pt), "v"(nx_fp), "v"(nx_np), "v"(nx_gid), "v"(nx_r[0]), "v"(nx_r[1]));
+      // The point scales of the factor phase are requested HERE, on every lane, and travel under the two barriers and the emission.
+      // (At the pass top, under `tid < np` and in front of the other loads, the compiler drained the counter behind them: wave 0 took
+      // an HBM round trip before any other load of its pass went out, and the values occupied six registers across the loop.)
+      // v2_passpt is padded with point 0 (plan.hpp), so every lane's index is a point that exists; only lanes < np use the values,
+      // and the diagonal-only pass (mode 1, once per handle) issues the three loads for nothing.
+      // Two things hold them in place: the memory clobber of barrier P2a's asm keeps the loads from sinking to their use, and the
+      // empty asm behind barrier P2 takes them as inputs, so they count as arrived there on every path (left pending under
+      // `tid < np`, they make the compiler drain the counter, the kernel's write-through stores included, in the Z phase and in
+      // emit_tile).
+      const double fsg0 = d.sigP[3 * (size_t)fp], fsg1 = d.sigP[3 * (size_t)fp + 1], fsg2 = d.sigP[3 * (size_t)fp + 2];
       STAMP(7);
       lds_barrier();                                                                                    // ---- barrier P2a: every accumulator has taken its last step
       if (mode == 0) zero_zd(krows);
       lds_barrier();                                                                                    // ---- barrier P2
+      asm volatile("" :: "v"(fsg0), "v"(fsg1), "v"(fsg2));
       if (det) wait_for(turn, my_turn);
       if (cnt > 0) {
         const double Am[3][3] = {{A[0], A[1], A[2]}, {A[1], A[3], A[4]}, {A[2], A[4], A[5]}};
@@ -658,7 +672,7 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
         }
       }
       hbase += kmax;
-      asm volatile("" :: "v"(nx_si), "v"(nx_pt), "v"(nx_fp), "v"(nx_np), "v"(nx_gid0), "v"(nx_r[0]), "v"(nx_r[1]));
+      asm volatile("" :: "v"(nx_si), "v"(nx_pt), "v"(nx_np), "v"(nx_r[0]), "v"(nx_r[1]));   // (the factor phase's point index and the group index are the evaluators')
       LaneGeom q;
       STAMPB(1);
       lane_geom(flo + lf, pt, q);                       // in flight while the Z matrix is zero-filled
