@@ -6,7 +6,8 @@
  *   CameraCalibration::readDepthData (per image point)   src/CameraCalibration.cpp:385-448   -> lifcal_depth_sample
  *   CameraModel::projectPointBack                        src/CameraModel.h:26-81             -> lifcal_depth_back_project_points
  *   its use on the image points of a frame               src/CameraCalibration.cpp:1274-1285
- * and adds the dense form (every pixel of a depth map, lifcal_depth_back_project_maps).  The PNG files stay with the caller (the
+ * and adds the dense form (every pixel of a depth map, lifcal_depth_back_project_maps) and, in parts (d)-(f), the forward model and
+ * the maps of several frames against each other (check and fusion).  The PNG files stay with the caller (the
  * Python side decodes them); a map here is the decoded image: [height][width] uint16, row-major, pixel (col, row) is the
  * virtual-image point (x_v, y_v) = (col, row).
  *
@@ -106,6 +107,87 @@ typedef struct lifcal_depth_maps {
   double seconds;          /* out: device time of the kernel (HIP events) */
 } lifcal_depth_maps;
 int lifcal_depth_back_project_maps(lifcal_depth_handle* h, const lifcal_depth_camera* cam, lifcal_depth_maps* io);
+
+/* ---- (d) the forward model: what projectPointBack inverts, in closed form, fp64, one lane per point ----
+ * With fr and views (they go together) p are world points and p_c = R p + t; without them p are camera coordinates.
+ *   x_u = X / Z * bL0, y_u likewise; delta = radialDistortion(x_u, y_u) + tangentialDistortion(x_u, y_u) (src/CameraModel.h:205-241)
+ *   b = fL Z / (Z - fL), v = (b - bL0) / B, x_v = (x_u + delta_x) (bL0 + v B) / bL0 / spx + cx, y_v likewise with spy, cy.
+ * A point is invalid when a coordinate is not finite, Z <= 0, Z == fL or v is not > 0: NaN in x, y, vdepth, counted in n_invalid. */
+typedef struct lifcal_depth_forward {
+  uint64_t n;
+  const double* p;        /* [3n] */
+  const uint32_t* fr;     /* [n] frame of the point, or NULL */
+  const double* views;    /* [6 n_frames], or NULL */
+  uint32_t n_frames;
+  uint32_t reserved;
+  double* x;              /* [n] out: x_v */
+  double* y;              /* [n] out: y_v */
+  double* vdepth;         /* [n] out */
+  uint64_t n_invalid;     /* out */
+} lifcal_depth_forward;
+int lifcal_depth_project_points(int32_t device, const lifcal_depth_camera* cam, lifcal_depth_forward* io);
+
+/* ---- (e) every map of a batch against its neighbours ----
+ * Source map s is checked against the targets t of the batch with 0 < |t - s| <= span.  Per valid source pixel (direct rule) and
+ * target: back-project as in (c), go into the target's camera (RT_t RT_s^-1), apply (d) -> (x_t, y_t, v_pred), take the target
+ * pixel ((int)(x_t + 0.5), (int)(y_t + 0.5)) (C truncation, outside the image as in lifcal_depth_sample), decode it by the direct
+ * rule -> v_obs, e = 1 / v_obs - 1 / v_pred.  Classes:
+ *   no data      (d) invalid, or the target pixel outside the image or invalid
+ *   consistent   |e| <= tol_iv
+ *   occluded     e < -tol_iv  (the target sees something nearer)
+ *   violation    e >  tol_iv  (the target sees through the point)
+ * sum_e / sum_e2 are formed per workgroup in a fixed tree and the workgroups are added in ascending order: two calls give the
+ * same bits. */
+typedef struct lifcal_depth_pair_stats {
+  uint64_t n_valid;        /* valid pixels of the source map */
+  uint64_t n_compared;     /* of these: consistent + occluded + violation */
+  uint64_t n_consistent, n_occluded, n_violation;
+  double sum_e, sum_e2;    /* over the consistent pixels */
+} lifcal_depth_pair_stats;
+
+typedef struct lifcal_depth_views {
+  int32_t first, count;    /* maps first .. first+count-1 of the handle, count >= 1 */
+  uint32_t span;           /* 1 .. 127 */
+  int32_t out_on_device;   /* 0: support / conflict / pair are host pointers, 1: device pointers on the handle's device */
+  uint32_t n_frames;
+  uint32_t reserved;
+  const uint32_t* frame;   /* [count] host: frame of each map */
+  const double* views;     /* [6 n_frames] host */
+  double tol_iv;           /* >= 0, in inverse virtual depth; one raw step is 1 / 65535 */
+  uint8_t* support;        /* [count][height][width] or NULL: targets in class consistent; 0 on invalid source pixels */
+  uint8_t* conflict;       /* [count][height][width] or NULL: targets in class violation */
+  lifcal_depth_pair_stats* pair;   /* [count][2 span] or NULL: slot j of source s is target s + j - span for j < span and
+                                      s + j - span + 1 otherwise; slots whose target lies outside the batch are all zero */
+  double seconds;          /* out: device time (HIP events) */
+} lifcal_depth_views;
+int lifcal_depth_check_maps(lifcal_depth_handle* h, const lifcal_depth_camera* cam, lifcal_depth_views* io);
+
+/* ---- (f) one cloud from a batch of maps ----
+ * A source pixel emits one point when it is valid, support >= min_support, conflict <= max_conflict (both as in (e), the pixel's
+ * own counts) and no target with a smaller map index is consistent with it (it defers to the lower map).  The point is
+ * sum w_k p_k / sum w_k over the pixel's own world point and the world points of the target pixels it was consistent with (the
+ * sampled pixel's centre with its own v_obs through the target's pose), added in ascending t, with
+ * w = 1 / (g v^2)^2, g = dz/dv = -B fL^2 / (b - fL)^2, b = bL0 + v B: the inverse variance of z for noise uniform in 1 / v.
+ * Points come out in ascending src, two calls give the same bits.  n_points is the number that qualified; when capacity is
+ * smaller the first `capacity` are written and the call still returns LIFCAL_BA_OK. */
+typedef struct lifcal_depth_fusion {
+  int32_t first, count;
+  uint32_t span;
+  int32_t out_on_device;   /* 0: xyz / n_merged / src are host pointers, 1: device pointers on the handle's device */
+  uint32_t n_frames;
+  int32_t out_double;      /* 0: xyz is float, 1: double */
+  const uint32_t* frame;   /* [count] host */
+  const double* views;     /* [6 n_frames] host */
+  double tol_iv;
+  uint32_t min_support, max_conflict;
+  uint64_t capacity;       /* points xyz / n_merged / src have room for; 0: count only */
+  void* xyz;               /* [capacity][3] world coordinates */
+  uint8_t* n_merged;       /* [capacity] or NULL: 1 + support */
+  uint32_t* src;           /* [capacity] or NULL: (m - first) height width + row width + col */
+  uint64_t n_points;       /* out */
+  double seconds;          /* out */
+} lifcal_depth_fusion;
+int lifcal_depth_fuse_maps(lifcal_depth_handle* h, const lifcal_depth_camera* cam, lifcal_depth_fusion* io);
 
 #ifdef __cplusplus
 }

@@ -283,6 +283,33 @@ class DepthMapsArgs(C.Structure):    # lifcal_depth_maps
                 ("n_invalid", C.c_uint64), ("seconds", C.c_double)]
 
 
+class DepthForward(C.Structure):     # lifcal_depth_forward
+    _fields_ = [("n", C.c_uint64), ("p", dptr), ("fr", uptr), ("views", dptr), ("n_frames", C.c_uint32), ("reserved", C.c_uint32),
+                ("x", dptr), ("y", dptr), ("vdepth", dptr), ("n_invalid", C.c_uint64)]
+
+
+class DepthPairStats(C.Structure):   # lifcal_depth_pair_stats
+    _fields_ = [("n_valid", C.c_uint64), ("n_compared", C.c_uint64), ("n_consistent", C.c_uint64), ("n_occluded", C.c_uint64), ("n_violation", C.c_uint64),
+                ("sum_e", C.c_double), ("sum_e2", C.c_double)]
+
+
+# the same row as a numpy structured dtype (the pair table is an array of it)
+DEPTH_PAIR_DTYPE = np.dtype([("n_valid", "<u8"), ("n_compared", "<u8"), ("n_consistent", "<u8"), ("n_occluded", "<u8"), ("n_violation", "<u8"),
+                             ("sum_e", "<f8"), ("sum_e2", "<f8")])
+
+
+class DepthViewsArgs(C.Structure):   # lifcal_depth_views
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("span", C.c_uint32), ("out_on_device", C.c_int32), ("n_frames", C.c_uint32), ("reserved", C.c_uint32),
+                ("frame", uptr), ("views", dptr), ("tol_iv", C.c_double), ("support", C.c_void_p), ("conflict", C.c_void_p), ("pair", C.c_void_p),
+                ("seconds", C.c_double)]
+
+
+class DepthFusionArgs(C.Structure):  # lifcal_depth_fusion
+    _fields_ = [("first", C.c_int32), ("count", C.c_int32), ("span", C.c_uint32), ("out_on_device", C.c_int32), ("n_frames", C.c_uint32), ("out_double", C.c_int32),
+                ("frame", uptr), ("views", dptr), ("tol_iv", C.c_double), ("min_support", C.c_uint32), ("max_conflict", C.c_uint32), ("capacity", C.c_uint64),
+                ("xyz", C.c_void_p), ("n_merged", C.c_void_p), ("src", C.c_void_p), ("n_points", C.c_uint64), ("seconds", C.c_double)]
+
+
 # every symbol include/lifcal_depth.h declares
 DEPTH_PROTOTYPES = {
     "lifcal_depth_create": (C.c_int, [C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_void_p)]),
@@ -291,6 +318,9 @@ DEPTH_PROTOTYPES = {
     "lifcal_depth_sample": (C.c_int, [C.c_void_p, C.c_uint64, dptr, dptr, _iptr, dptr, C.POINTER(DepthSampleCounts)]),
     "lifcal_depth_back_project_points": (C.c_int, [C.c_int32, C.POINTER(DepthCamera), C.POINTER(DepthPoints)]),
     "lifcal_depth_back_project_maps": (C.c_int, [C.c_void_p, C.POINTER(DepthCamera), C.POINTER(DepthMapsArgs)]),
+    "lifcal_depth_project_points": (C.c_int, [C.c_int32, C.POINTER(DepthCamera), C.POINTER(DepthForward)]),
+    "lifcal_depth_check_maps": (C.c_int, [C.c_void_p, C.POINTER(DepthCamera), C.POINTER(DepthViewsArgs)]),
+    "lifcal_depth_fuse_maps": (C.c_int, [C.c_void_p, C.POINTER(DepthCamera), C.POINTER(DepthFusionArgs)]),
 }
 
 class ResectProblem(C.Structure):    # include/lifcal_resect.h lifcal_resect_problem

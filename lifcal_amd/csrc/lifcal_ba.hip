@@ -1628,6 +1628,9 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 // depth-map sampling, back-projection to metric 3D and the object-space comparison (include/lifcal_depth.h, include/lifcal_ba.h)
 #include "depth.hpp"
 
+// depth maps of several frames against each other: forward model, cross-view check, fusion (include/lifcal_depth.h (d)-(f))
+#include "depth_views.hpp"
+
 // batched pose resection of frames against a constant camera and constant points (include/lifcal_resect.h)
 #include "resection.hpp"
 

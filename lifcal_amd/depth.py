@@ -4,6 +4,9 @@
     DepthMaps.sample()               <- its per-point part for already decoded images (:385-448)
     DepthMaps.backProjectPoints()    <- CameraModel::projectPointBack as storeResults uses it (src/CameraModel.h:26-81, :1274-1285)
     DepthMaps.backProjectMaps()      <- the same for every pixel of a batch of depth maps (metric point cloud of a frame)
+    projectPoints()                  the forward model projectPointBack inverts: 3D point -> (x_v, y_v, virtual depth)
+    DepthMaps.checkMaps()            the maps of neighbouring frames against each other through the camera and the poses
+    DepthMaps.fuseMaps()             one cloud from a batch of maps, filtered by that agreement
 The arithmetic runs on the GPU inside liblifcal_ba.so; there is no Python or CPU fallback.  Only the PNG container is decoded
 here (zlib + struct, 16-bit grayscale non-interlaced files as the reference's depth images are).
 """
@@ -104,6 +107,75 @@ def backProjectPoints(x, y, vdepth, cam, config: int, spx: float, spy: Optional[
         cov = np.zeros((n, 6)); io.cov_pc = capi.as_dptr(cov)
     _check(lib.lifcal_depth_back_project_points(int(device), C.byref(dc), C.byref(io)), "lifcal_depth_back_project_points")
     return BackProjection(p_c, p_w, jac, dv, cov, int(io.n_invalid))
+
+
+STEP_IV = 1.0 / 65535.0   # one raw step of inverse virtual depth
+
+
+@dataclass
+class ForwardProjection:
+    """x, y: (n,) virtual-image coordinates; vdepth: (n,); NaN rows for invalid points, n_invalid of them."""
+    x: np.ndarray
+    y: np.ndarray
+    vdepth: np.ndarray
+    n_invalid: int
+
+
+@dataclass
+class ViewCheck:
+    """support, conflict: (count, H, W) uint8 (numpy, or torch tensors with device_out); pair: (count, 2 span) structured array
+    (_capi.DEPTH_PAIR_DTYPE), slot j of source s is target s + j - span for j < span, s + j - span + 1 otherwise."""
+    support: object
+    conflict: object
+    pair: np.ndarray
+    span: int
+    seconds: float
+
+    def rms_steps(self) -> np.ndarray:
+        """RMS of e over the consistent pixels of every pair slot, in raw steps of inverse virtual depth; NaN without any"""
+        n = self.pair["n_consistent"].astype(np.float64)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return np.sqrt(self.pair["sum_e2"] / n) / STEP_IV
+
+    def target(self, s: int, j: int) -> int:
+        return s + j - self.span + (1 if j >= self.span else 0)
+
+
+@dataclass
+class FusedCloud:
+    """xyz: (n, 3) world coordinates; n_merged: (n,) uint8 = 1 + support; src: (n,) uint32 = (m - first) H W + row W + col, ascending;
+    n_points: the number that qualified (n = min(n_points, capacity))."""
+    xyz: object
+    n_merged: object
+    src: object
+    n_points: int
+    seconds: float
+
+
+def projectPoints(p, cam, config: int, spx: float, spy: Optional[float] = None, fr=None, views=None, device: int = 0) -> ForwardProjection:
+    """The forward model projectPointBack inverts, in closed form: 3D points (n, 3) -> (x_v, y_v, virtual depth).  With fr and
+    views the points are world points (p_c = R p + t), without them camera coordinates."""
+    p = np.ascontiguousarray(p, np.float64)
+    if p.size % 3 != 0 or (p.ndim > 1 and p.shape[-1] != 3):
+        raise LifcalError("projectPoints: p must be (n, 3)")
+    p = p.reshape(-1)
+    n = len(p) // 3
+    dc = depth_camera(cam, config, spx, spy)
+    io = capi.DepthForward()
+    io.n = n; io.p = capi.as_dptr(p)
+    keep = []
+    if fr is not None or views is not None:
+        if fr is None or views is None:
+            raise LifcalError("projectPoints: fr and views go together")
+        fr_a = np.ascontiguousarray(fr, np.uint32).reshape(-1); vw = np.ascontiguousarray(views, np.float64).reshape(-1)
+        if len(fr_a) != n:
+            raise LifcalError("projectPoints: fr differs in length")
+        keep += [fr_a, vw]
+        io.fr, io.views, io.n_frames = capi.as_uptr(fr_a), capi.as_dptr(vw), len(vw) // 6
+    x = np.zeros(n); y = np.zeros(n); v = np.zeros(n)
+    io.x, io.y, io.vdepth = capi.as_dptr(x), capi.as_dptr(y), capi.as_dptr(v)
+    _check(capi.load_library().lifcal_depth_project_points(int(device), C.byref(dc), C.byref(io)), "lifcal_depth_project_points")
+    return ForwardProjection(x, y, v, int(io.n_invalid))
 
 
 class DepthMaps:
@@ -225,6 +297,115 @@ class DepthMaps:
             io.sigma_z = ptr(sz) if sz is not None else None
         _check(self._lib.lifcal_depth_back_project_maps(self._h, C.byref(dc), C.byref(io)), "lifcal_depth_back_project_maps")
         return DenseBackProjection(xyz, z, sz, int(io.n_invalid), float(io.seconds))
+
+    def projectPoints(self, p, cam, config: int, spx: float, **kw) -> ForwardProjection:
+        return projectPoints(p, cam, config, spx, device=self.device, **kw)
+
+    def _views_io(self, io, who: str, frame, views, span, tol_steps, first, count):
+        count = self.max_maps - int(first) if count is None else int(count)
+        fr_a, vw = views_arguments(who, count, frame, views, span, tol_steps)
+        io.first, io.count, io.span, io.n_frames = int(first), count, int(span), len(vw) // 6
+        io.frame, io.views, io.tol_iv = capi.as_uptr(fr_a), capi.as_dptr(vw), float(tol_steps) * STEP_IV
+        return count, (fr_a, vw)
+
+    def checkMaps(self, cam, config: int, spx: float, frame, views, span: int = 1, tol_steps: float = 4.0, first: int = 0, count: Optional[int] = None,
+                  spy: Optional[float] = None, want_support: bool = True, want_conflict: bool = True, device_out: bool = False) -> ViewCheck:
+        """Every map of first .. first+count-1 against the maps of the batch at most `span` away, through the camera and the poses
+        views[frame[m]]: per source pixel the number of targets that agree (support) and that see through it (conflict), per
+        (source, target) the class counts and the sums of e = 1/v_obs - 1/v_pred over the agreeing pixels.  tol_steps: the
+        tolerance in raw steps (1 / 65535) of inverse virtual depth.  device_out: support / conflict are torch tensors."""
+        dc = depth_camera(cam, config, spx, spy)
+        io = capi.DepthViewsArgs()
+        count, keep = self._views_io(io, "checkMaps", frame, views, span, tol_steps, first, count)
+        shape = (count, self.height, self.width)
+        pair = np.zeros((count, 2 * int(span)), capi.DEPTH_PAIR_DTYPE)
+        if device_out:
+            import torch
+            dev = torch.device("cuda", self.device)
+            mk = lambda: torch.zeros(shape, dtype=torch.uint8, device=dev)
+            ptr = lambda t: C.c_void_p(t.data_ptr())
+            pair_t = torch.zeros(pair.nbytes, dtype=torch.uint8, device=dev)
+            torch.cuda.synchronize(dev)
+            io.out_on_device, io.pair = 1, ptr(pair_t)
+        else:
+            mk = lambda: np.zeros(shape, np.uint8)
+            ptr = lambda a: C.c_void_p(a.ctypes.data)
+            io.pair = C.c_void_p(pair.ctypes.data)
+        support = mk() if want_support else None
+        conflict = mk() if want_conflict else None
+        io.support = ptr(support) if support is not None else None
+        io.conflict = ptr(conflict) if conflict is not None else None
+        _check(self._lib.lifcal_depth_check_maps(self._h, C.byref(dc), C.byref(io)), "lifcal_depth_check_maps")
+        if device_out:
+            pair = np.frombuffer(pair_t.cpu().numpy().tobytes(), capi.DEPTH_PAIR_DTYPE).reshape(pair.shape).copy()
+        del keep
+        return ViewCheck(support, conflict, pair, int(span), float(io.seconds))
+
+    def fuseMaps(self, cam, config: int, spx: float, frame, views, span: int = 1, tol_steps: float = 4.0, min_support: int = 1, max_conflict: int = 0,
+                 capacity: Optional[int] = None, first: int = 0, count: Optional[int] = None, spy: Optional[float] = None, out_double: bool = False,
+                 device_out: bool = False) -> FusedCloud:
+        """One cloud from maps first .. first+count-1: a valid pixel with support >= min_support and conflict <= max_conflict (see
+        checkMaps) that is not consistent with a lower map emits the depth-weighted mean of its own world point and those of the
+        target pixels it agrees with.  Points come in ascending src.  capacity: room for that many points (default: all that
+        qualify, found by a counting call first); fewer than n_points keeps the ordered prefix."""
+        if min_support < 0 or max_conflict < 0 or (capacity is not None and capacity < 0):
+            err = LifcalError("fuseMaps: min_support, max_conflict and capacity must not be negative (-1)")
+            err.code = -1
+            raise err
+        dc = depth_camera(cam, config, spx, spy)
+        io = capi.DepthFusionArgs()
+        count, keep = self._views_io(io, "fuseMaps", frame, views, span, tol_steps, first, count)
+        io.min_support, io.max_conflict, io.out_double = int(min_support), min(int(max_conflict), 0xFFFFFFFF), 1 if out_double else 0
+        if capacity is None:
+            io.capacity = 0
+            _check(self._lib.lifcal_depth_fuse_maps(self._h, C.byref(dc), C.byref(io)), "lifcal_depth_fuse_maps")
+            capacity = int(io.n_points)
+        cap = int(capacity)
+        if device_out:
+            import torch
+            dev = torch.device("cuda", self.device)
+            xyz = torch.zeros((cap, 3), dtype=torch.float64 if out_double else torch.float32, device=dev)
+            merged = torch.zeros(cap, dtype=torch.uint8, device=dev); src = torch.zeros(cap, dtype=torch.int32, device=dev)   # the bits of uint32
+            ptr = lambda t: C.c_void_p(t.data_ptr())
+            torch.cuda.synchronize(dev)
+            io.out_on_device = 1
+        else:
+            xyz = np.zeros((cap, 3), np.float64 if out_double else np.float32)
+            merged = np.zeros(cap, np.uint8); src = np.zeros(cap, np.uint32)
+            ptr = lambda a: C.c_void_p(a.ctypes.data)
+        io.capacity = cap
+        if cap:
+            io.xyz, io.n_merged, io.src = ptr(xyz), ptr(merged), ptr(src)
+        _check(self._lib.lifcal_depth_fuse_maps(self._h, C.byref(dc), C.byref(io)), "lifcal_depth_fuse_maps")
+        n = min(int(io.n_points), cap)
+        del keep
+        return FusedCloud(xyz[:n], merged[:n], src[:n], int(io.n_points), float(io.seconds))
+
+
+def views_arguments(who: str, count: int, frame, views, span, tol_steps):
+    """The checks checkMaps and fuseMaps make before anything reaches the device: (frame as uint32, views flat).  A bad argument
+    raises LifcalError with code -1 (LIFCAL_BA_ERR_INVALID_ARG)."""
+    def bad(msg):
+        err = LifcalError(f"{who}: {msg} (-1)")
+        err.code = -1
+        return err
+    if frame is None or views is None:
+        raise bad("frame and views are required")
+    if int(count) <= 0:
+        raise bad("count must be positive")
+    if int(span) != span or int(span) < 1 or int(span) > 127:
+        raise bad("span must be in 1 .. 127")
+    if not float(tol_steps) >= 0.0:
+        raise bad("the tolerance must be a number >= 0")
+    vw = np.ascontiguousarray(views, np.float64).reshape(-1)
+    if len(vw) % 6 != 0:
+        raise bad("views must hold six values per frame")
+    f = np.asarray(frame).reshape(-1)
+    if len(f) != int(count):
+        raise bad("one frame index per map")
+    if np.any(f < 0):
+        raise bad("frame indices must not be negative")
+    return np.ascontiguousarray(f, np.uint32), vw
 
 
 # ------------------------------------------------------------------------------------------------ PNG container

@@ -106,6 +106,17 @@ def storeCameraCoordinates(dir_results: str, folder: str, frame_ids, fr, xyz):
         _ok(lib.lifcal_write_camera_coordinates_ply(d.encode(), int(fid), len(sel), capi.as_dptr(sel)), "storeCameraCoordinates")
 
 
+def storeFusedCloudPly(dir_results: str, xyz, name: str = "fusedCloud.ply"):
+    """The cloud of DepthMaps.fuseMaps (FusedCloud.xyz, world coordinates) in the format of objectCoordinates.ply (:1131-1144);
+    a caller writes it next to the per-frame clouds of storeCameraCoordinates (:1218-1287)."""
+    if hasattr(xyz, "cpu"):
+        xyz = xyz.cpu().numpy()
+    p = np.ascontiguousarray(xyz, np.float64)
+    if p.ndim != 2 or p.shape[1] != 3:
+        raise LifcalError("storeFusedCloudPly: xyz must be (n, 3)")
+    _ok(capi.load_library().lifcal_write_object_coordinates_ply(os.path.join(dir_results, name).encode(), len(p), capi.as_dptr(p)), "storeFusedCloudPly")
+
+
 def _group_csv(path: str, id_header: str, table, ids=None, xy=None):
     rows = np.ascontiguousarray(table.rows if hasattr(table, "rows") else table, capi.GROUP_STATS_DTYPE)
     ids = None if ids is None else np.ascontiguousarray(ids, np.int32).reshape(-1)
