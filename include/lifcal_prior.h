@@ -14,8 +14,12 @@
  * The result of a sweep or a solve with priors has the same bits on every run as far as the prior is concerned, whatever
  * options.deterministic says: every word receives one add from the prior kernel, in stream order behind the sweep kernels.
  *
- * Not covered: priors on 3D points, priors that couple camera and poses or two poses, handles with world_size > 1
- * (LIFCAL_BA_ERR_INVALID_ARG), and lifcal_ba_solve_windowed, which creates its own handles and carries no priors.
+ * Priors on 3D points are the second part of this header: one 3 x 3 information matrix per control point,
+ * the point set fixed when the handle is created.
+ *
+ * Not covered: points held exactly constant, priors that couple camera and poses, two poses, two points or a point with a pose,
+ * handles with world_size > 1 and lifcal_ba_create_shard (LIFCAL_BA_ERR_INVALID_ARG), and lifcal_ba_solve_windowed, which creates
+ * its own handles and carries no priors.
  */
 #ifndef LIFCAL_PRIOR_H
 #define LIFCAL_PRIOR_H
@@ -55,6 +59,45 @@ int lifcal_ba_prior_cost(lifcal_ba_handle* h, double* cam_cost, double* pose_cos
  * null; *rank (may be NULL) receives the number kept, and info is the Moore-Penrose inverse of the sub-matrix over that many of its
  * largest eigenvalues.  Pass estimable_mask for the camera block, 0x3F for a pose block. */
 int lifcal_prior_from_covariance(const double* cov, uint32_t n, uint64_t use_mask, double rcond, double* info, uint32_t* rank);
+
+/* ---- priors on 3D points: control points with known coordinates ----
+ *
+ * 1/2 d^T Lambda d with d = P - mean per prior-ed point, what Ceres computes for one extra residual block Lambda^(1/2) d without a
+ * loss function.  It adds to the cost (sweep, candidate, initial_cost / final_cost), to the point gradient, to the point block U_p
+ * and to the Hessian diagonal behind the Jacobi scaling and the LM clamp, and through them to the Schur complement, rhs, the
+ * back-substitution and the gradient norm.  A prior on an endpoint of a distance constraint (eliminated or promoted) and on a point
+ * without observations is supported.  A problem without LIFCAL_BA_CFG_REFINE_POINTS (or without refined poses: the points are no
+ * parameters then) drops the term: cost 0, nothing added.  lifcal_ba_reproj_stats and the residual report see observations only.
+ * Three or more control points that are not collinear fix datum and scale of a scene.
+ *
+ * The planner treats prior-ed points like constraint points, so the point set belongs to the handle's layout and is fixed at
+ * create; means and matrices can be replaced afterwards.  The prior's contribution has the same bits on every run, whatever
+ * options.deterministic says. */
+typedef struct lifcal_ba_point_priors {
+  uint32_t n, reserved;
+  const uint32_t* point;   /* [n] strictly ascending point ids */
+  const double*   mean;    /* [3n] */
+  const double*   info;    /* [9n] row-major, symmetric PSD 3x3 information matrices */
+} lifcal_ba_point_priors;
+
+/* Host only.  The rules and codes of lifcal_ba_check_priors on 3 x 3 matrices: LIFCAL_BA_ERR_INVALID_ARG for a null array with n > 0,
+ * a non-finite entry, an asymmetric matrix, a negative diagonal entry, an eigenvalue below -1e-12 lambda_max, ids not strictly
+ * ascending; LIFCAL_BA_ERR_OUT_OF_RANGE for a point id >= n_points. */
+int lifcal_ba_check_point_priors(uint32_t n_points, const lifcal_ba_point_priors* p);
+
+/* lifcal_ba_create with control points.  p == NULL or n == 0: exactly lifcal_ba_create (same layout, same results).  Checks first
+ * (lifcal_ba_check_point_priors); options.world_size > 1 with n > 0 is LIFCAL_BA_ERR_INVALID_ARG.  The matrices are symmetrised. */
+int lifcal_ba_create_with_point_priors(const lifcal_ba_problem* problem, const lifcal_ba_point_priors* p,
+                                       const lifcal_ba_options* options, lifcal_ba_handle** out);
+
+/* New means and matrices on the SAME point set (p == NULL: every matrix zero, the term leaves).  LIFCAL_BA_ERR_INVALID_ARG, with the
+ * handle left as it was, for a handle that lifcal_ba_create_with_point_priors did not create and for a point set that differs from
+ * the one given there; the codes of lifcal_ba_check_point_priors otherwise.  New values start a new solve: the Jacobi scaling is
+ * taken again at the next sweep. */
+int lifcal_ba_set_point_priors(lifcal_ba_handle* h, const lifcal_ba_point_priors* p);
+
+/* Sum of 1/2 d^T Lambda d over the point priors at the device-resident points.  0 without priors or where the term is dropped. */
+int lifcal_ba_point_prior_cost(lifcal_ba_handle* h, double* cost);
 
 #ifdef __cplusplus
 }

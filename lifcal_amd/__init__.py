@@ -5,7 +5,8 @@ the host mirror of the reference entry points and the synthetic scene generator.
 """
 from . import _capi, scene  # noqa: F401
 from .bundle_adjustment import (BundleAdjustment, Covariance, LifcalError, make_config, plan, plan_stats, plan_shape, comm_unique_id, initPlenopticParameters,  # noqa: F401
-                                performBundleAdjustmentWindowed, GroupTable, ResidualReport, sensor_cells, check_priors, prior_from_covariance)
+                                performBundleAdjustmentWindowed, GroupTable, ResidualReport, sensor_cells, check_priors, prior_from_covariance,
+                                check_point_priors, alignFit, alignApply, alignScene, Alignment)
 from .mla import MicroLensGrid, RawObservations  # noqa: F401
 from .depth import DepthMaps, backProjectPoints, projectPoints, readDepthData, read_png16, depth_is_estimable  # noqa: F401
 from .resection import resectFrames, ResectionResult  # noqa: F401

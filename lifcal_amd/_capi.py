@@ -450,8 +450,27 @@ class Priors(C.Structure):              # include/lifcal_prior.h lifcal_ba_prior
                 ("pose_frame", uptr), ("pose_mean", dptr), ("pose_info", dptr)]
 
 
+class PointPriors(C.Structure):         # include/lifcal_prior.h lifcal_ba_point_priors
+    _fields_ = [("n", C.c_uint32), ("reserved", C.c_uint32), ("point", uptr), ("mean", dptr), ("info", dptr)]
+
+
+class Alignment(C.Structure):           # include/lifcal_align.h lifcal_alignment
+    _fields_ = [("scale", C.c_double), ("R", C.c_double * 9), ("t", C.c_double * 3), ("rms", C.c_double),
+                ("n_used", C.c_uint32), ("reserved", C.c_uint32)]
+
+
+# every symbol include/lifcal_align.h declares
+ALIGN_PROTOTYPES = {
+    "lifcal_align_fit": (C.c_int, [C.c_uint32, dptr, dptr, dptr, C.c_int32, C.POINTER(Alignment)]),
+    "lifcal_align_apply": (C.c_int, [C.POINTER(Alignment), C.c_uint32, dptr, C.c_uint64, dptr]),
+}
+
 # every symbol include/lifcal_prior.h declares
 PRIOR_PROTOTYPES = {
+    "lifcal_ba_check_point_priors": (C.c_int, [C.c_uint32, C.POINTER(PointPriors)]),
+    "lifcal_ba_create_with_point_priors": (C.c_int, [C.c_void_p, C.POINTER(PointPriors), C.c_void_p, C.POINTER(C.c_void_p)]),
+    "lifcal_ba_set_point_priors": (C.c_int, [C.c_void_p, C.POINTER(PointPriors)]),
+    "lifcal_ba_point_prior_cost": (C.c_int, [C.c_void_p, dptr]),
     "lifcal_ba_check_priors": (C.c_int, [C.c_uint32, C.POINTER(Priors)]),
     "lifcal_ba_set_priors": (C.c_int, [C.c_void_p, C.POINTER(Priors)]),
     "lifcal_ba_prior_cost": (C.c_int, [C.c_void_p, dptr, dptr]),
@@ -480,6 +499,22 @@ class PriorArrays:
                 raise ValueError("pose priors: frames[n], means[n, 6] and infos[n, 6, 6]")
             p.n_pose_priors = n
             p.pose_frame, p.pose_mean, p.pose_info = as_uptr(self.pose_frame), as_dptr(self.pose_mean), as_dptr(self.pose_info)
+        self.struct = p
+
+
+class PointPriorArrays:
+    """Owns contiguous copies of the arrays of a lifcal_ba_point_priors: ids[n] strictly ascending, means[n, 3], infos[n, 3, 3]."""
+
+    def __init__(self, ids, means, infos):
+        self.point = np.ascontiguousarray(np.asarray(ids, dtype=np.uint32).reshape(-1)).copy()
+        self.mean = np.ascontiguousarray(np.asarray(means, dtype=np.float64).reshape(-1)).copy()
+        self.info = np.ascontiguousarray(np.asarray(infos, dtype=np.float64).reshape(-1)).copy()
+        n = self.point.shape[0]
+        if self.mean.shape[0] != 3 * n or self.info.shape[0] != 9 * n:
+            raise ValueError("point priors: ids[n], means[n, 3] and infos[n, 3, 3]")
+        p = PointPriors()
+        p.n = n
+        p.point, p.mean, p.info = as_uptr(self.point), as_dptr(self.mean), as_dptr(self.info)
         self.struct = p
 
 
@@ -542,7 +577,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

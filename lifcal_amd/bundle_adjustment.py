@@ -87,6 +87,71 @@ def check_priors(n_frames: int, camera=None, poses=None):
     _check(lib, lib.lifcal_ba_check_priors(int(n_frames), C.byref(arrs.struct)), "lifcal_ba_check_priors")
 
 
+def check_point_priors(n_points: int, ids, means, infos):
+    """Host-only check of a set of point priors (lifcal_ba_check_point_priors): raises LifcalError with .code
+    LIFCAL_BA_ERR_INVALID_ARG (-1) or LIFCAL_BA_ERR_OUT_OF_RANGE (-4); ids[n] strictly ascending, means[n, 3], infos[n, 3, 3]."""
+    lib = capi.load_library()
+    arrs = capi.PointPriorArrays(ids, means, infos)
+    _check(lib, lib.lifcal_ba_check_point_priors(int(n_points), C.byref(arrs.struct)), "lifcal_ba_check_point_priors")
+
+
+@dataclass
+class Alignment:
+    """to ~ scale * R from + t (lifcal_align_fit): rms over the n_used points with a positive weight."""
+    scale: float
+    R: np.ndarray
+    t: np.ndarray
+    rms: float
+    n_used: int
+
+    def _struct(self):
+        a = capi.Alignment()
+        a.scale = float(self.scale); a.rms = float(self.rms); a.n_used = int(self.n_used)
+        a.R[:] = [float(x) for x in np.asarray(self.R, np.float64).reshape(9)]
+        a.t[:] = [float(x) for x in np.asarray(self.t, np.float64).reshape(3)]
+        return a
+
+
+def alignFit(src, dst, weights=None, with_scale: bool = True) -> Alignment:
+    """Weighted closed-form dst ~ s R src + t over points src[n, 3], dst[n, 3] (Horn's quaternion method, lifcal_align_fit);
+    with_scale False forces s = 1.  LifcalError (.code -1) for fewer than three weighted points, collinear points on either side, non-finite input; ValueError for
+    arrays whose shapes disagree."""
+    lib = capi.load_library()
+    a = np.ascontiguousarray(np.asarray(src, np.float64).reshape(-1, 3))
+    b = np.ascontiguousarray(np.asarray(dst, np.float64).reshape(-1, 3))
+    if a.shape != b.shape:
+        raise ValueError("alignFit: src[n, 3] and dst[n, 3]")
+    w = None if weights is None else np.ascontiguousarray(np.asarray(weights, np.float64).reshape(-1))
+    if w is not None and w.shape[0] != a.shape[0]:
+        raise ValueError("alignFit: weights[n]")
+    out = capi.Alignment()
+    _check(lib, lib.lifcal_align_fit(a.shape[0], capi.as_dptr(a), capi.as_dptr(b), capi.as_dptr(w), 1 if with_scale else 0, C.byref(out)), "lifcal_align_fit")
+    return Alignment(out.scale, np.array(out.R[:]).reshape(3, 3), np.array(out.t[:]), out.rms, out.n_used)
+
+
+def alignApply(alignment: Alignment, views, pts):
+    """(views', pts'): the scene moved by the alignment (lifcal_align_apply): P' = s R P + t, R_f' = R_f R^T, t_f' = s t_f - R_f' t.
+    Copies; views[F, 6] and pts[P, 3] (either may be None)."""
+    lib = capi.load_library()
+    v = None if views is None else np.ascontiguousarray(np.asarray(views, np.float64).reshape(-1, 6)).copy()
+    p = None if pts is None else np.ascontiguousarray(np.asarray(pts, np.float64).reshape(-1, 3)).copy()
+    a = alignment._struct()
+    _check(lib, lib.lifcal_align_apply(C.byref(a), 0 if v is None else v.shape[0], capi.as_dptr(v), 0 if p is None else p.shape[0], capi.as_dptr(p)), "lifcal_align_apply")
+    return v, p
+
+
+def alignScene(problem_arrays, ids, coords, with_scale: bool = True, weights=None) -> Alignment:
+    """Moves the start values of a capi.ProblemArrays (views and pts, in place) onto control points: fits the current coordinates of
+    the points `ids` to `coords[n, 3]` and applies the result to every pose and point.  Returns the Alignment."""
+    ids = np.asarray(ids, np.int64).reshape(-1)
+    pts = problem_arrays.pts.reshape(-1, 3)
+    al = alignFit(pts[ids], coords, weights, with_scale)
+    v, p = alignApply(al, problem_arrays.views, problem_arrays.pts)
+    problem_arrays.views[:] = v.reshape(-1)
+    problem_arrays.pts[:] = p.reshape(-1)
+    return al
+
+
 def prior_from_covariance(cov, use_mask: int, rcond: float = 1e-9):
     """(info, rank): pseudo-inverse of the sub-matrix of the n x n covariance selected by the bits of use_mask, zero rows and
     columns elsewhere; eigenvalues below rcond * lambda_max of the Jacobi-scaled sub-matrix count as null
@@ -184,9 +249,12 @@ def sensor_cells(u, v, cell_px: float, raw_width: int, raw_height: int):
 class BundleAdjustment:
     """One bundle-adjustment problem resident on one MI355X (one rank of a point-sharded job)."""
 
-    def __init__(self, problem: capi.ProblemArrays, options: Optional[capi.Options] = None, partition: Optional["capi.PartitionArrays"] = None):
+    def __init__(self, problem: capi.ProblemArrays, options: Optional[capi.Options] = None, partition: Optional["capi.PartitionArrays"] = None,
+                 point_priors=None):
         """partition: `problem` is the rank's SHARD (only the observations of the points it owns, see capi.PartitionArrays.shard_of)
-        and the handle is made with lifcal_ba_create_shard; None: the whole problem, lifcal_ba_create."""
+        and the handle is made with lifcal_ba_create_shard; None: the whole problem, lifcal_ba_create.
+        point_priors = (ids[n] strictly ascending, means[n, 3], infos[n, 3, 3]): control points, the handle is made with
+        lifcal_ba_create_with_point_priors and keeps this point set (set_point_priors replaces the values); not with a partition."""
         self.lib = capi.load_library()
         self.problem = problem
         if options is None:
@@ -196,7 +264,15 @@ class BundleAdjustment:
         self._h = C.c_void_p()
         self._hook = None
         self._partition = partition
-        if partition is not None:
+        if point_priors is not None:
+            if partition is not None:
+                err = LifcalError("point priors are not supported on a shard handle (lifcal_ba_create_shard)")
+                err.code = -1
+                raise err
+            arrs = capi.PointPriorArrays(*point_priors) if len(point_priors) else None   # (): a NULL prior set, exactly lifcal_ba_create
+            _check(self.lib, self.lib.lifcal_ba_create_with_point_priors(C.byref(problem.struct), C.byref(arrs.struct) if arrs else None, C.byref(options), C.byref(self._h)),
+                   "lifcal_ba_create_with_point_priors")
+        elif partition is not None:
             _check(self.lib, self.lib.lifcal_ba_create_shard(C.byref(problem.struct), C.byref(partition.struct), C.byref(options), C.byref(self._h)), "lifcal_ba_create_shard")
         else:
             _check(self.lib, self.lib.lifcal_ba_create(C.byref(problem.struct), C.byref(options), C.byref(self._h)), "lifcal_ba_create")
@@ -296,6 +372,22 @@ class BundleAdjustment:
         c = np.zeros(2)
         _check(self.lib, self.lib.lifcal_ba_prior_cost(self._h, capi.as_dptr(c[0:1]), capi.as_dptr(c[1:2])), "lifcal_ba_prior_cost")
         return float(c[0]), float(c[1])
+
+    def set_point_priors(self, ids, means, infos):
+        """New means[n, 3] and infos[n, 3, 3] on the point set given at create (lifcal_ba_set_point_priors); a different set or a handle
+        made without point_priors raises LifcalError (.code -1) and leaves the handle as it was."""
+        arrs = capi.PointPriorArrays(ids, means, infos)
+        _check(self.lib, self.lib.lifcal_ba_set_point_priors(self._h, C.byref(arrs.struct)), "lifcal_ba_set_point_priors")
+
+    def clear_point_priors(self):
+        """Every information matrix zero: the term leaves, the point set (and the layout) stays."""
+        _check(self.lib, self.lib.lifcal_ba_set_point_priors(self._h, None), "lifcal_ba_set_point_priors")
+
+    def point_prior_cost(self) -> float:
+        """Sum of 1/2 d^T info d over the point priors at the device-resident points."""
+        c = np.zeros(1)
+        _check(self.lib, self.lib.lifcal_ba_point_prior_cost(self._h, capi.as_dptr(c)), "lifcal_ba_point_prior_cost")
+        return float(c[0])
 
     def covariance(self, gauge_frame: int = -1, want_pose_blocks: bool = True, scale_by_residual_variance: bool = False,
                    null_rcond: Optional[float] = None, estimable_tol: Optional[float] = None, want_pose_band: bool = False) -> Covariance:

@@ -23,7 +23,9 @@
 
 #include "../../include/lifcal_ba.h"
 #include "../../include/lifcal_prior.h"
+#include "../../include/lifcal_align.h"
 #include "kernels.hpp"
+#include "point_priors.hpp"
 #include "plan.hpp"
 #include "linesearch.hpp"
 #include "sweep_state.hpp"
@@ -154,6 +156,13 @@ struct lifcal_ba_handle {
   std::vector<double> pr_cam_mean, pr_cam_info, pr_pose_mean, pr_pose_info, pr_stage;
   std::vector<uint32_t> pr_frame;
   double* pr_buf = nullptr; uint32_t* pr_frame_dev = nullptr; size_t pr_cap = 0;
+  // Gaussian priors on 3D points (priors.hpp): the point set is fixed at lifcal_ba_create_with_point_priors (the planner put these
+  // points on the special path), values are replaced by lifcal_ba_set_point_priors.  pp_buf: cost word (2) | means 3n | matrices 9n
+  bool pp_entry = false, pp_active = false;
+  std::vector<uint32_t> pp_point;
+  std::vector<double> pp_info, pp_stage;   // the symmetrised matrices (covariance counts their rows), the upload's staging copy
+  double* pp_buf = nullptr; uint32_t* pp_point_dev = nullptr;
+  PointPriorSet pp{};                      // the device view k_point_priors takes
   bool trace = false;            // LIFCAL_TRACE=1: one stderr line per host decision of the LM loop, tagged with the rank
   double* Lpanel = nullptr; size_t bandw_lds = 0, backw_lds = 0; bool bandw_ok = false;
   CrPlan cr; bool use_cr = false;   // block odd-even reduction (bandchol3.hpp): long sequences
@@ -169,7 +178,7 @@ struct lifcal_ba_handle {
   bool prof_active() const { return prof_in_span() && prof_seen % prof_stride == 0; }
 };
 
-// Gaussian priors on camera and poses: k_priors, launch_priors and the C ABI of include/lifcal_prior.h
+// Gaussian priors on camera, poses and 3D points: k_priors, k_point_priors, their launchers and the C ABI of include/lifcal_prior.h
 #include "priors.hpp"
 
 namespace {
@@ -332,6 +341,7 @@ int launch_value_cost(lifcal_ba_handle* h, const CamConsts* camc, const double* 
   }
   launch_constraints(h, 1, pts, out);
   HIP_TRY(hipGetLastError());
+  if (int rc = launch_point_priors(h, 1, pts, out)) return rc;
   return launch_priors(h, 1, cam, views, out);
 }
 
@@ -397,6 +407,7 @@ int launch_blocks(lifcal_ba_handle* h, double radius, int mode) {
   }
   if (prof && !d.n_blocks) HIP_TRY(hipEventRecord(ev_b, h->stream));
   launch_constraints(h, 0, d.pts, d.scal + SCAL_COST);
+  if (int rc = launch_point_priors(h, 0, d.pts, d.scal + SCAL_COST)) return rc;   // (in front of k_promote_diag: a promoted point's prior diagonal goes with its slab)
   if (d.Q && d.use_points) hipLaunchKernelGGL(k_promote_diag, dim3((d.Q + 63) / 64), dim3(64), 0, h->stream, d);
   HIP_TRY(hipGetLastError());
   return launch_priors(h, 0, d.cam, d.views, d.scal + SCAL_COST);   // (both modes: the diagonal of the prior belongs to the Jacobi scaling)
@@ -830,7 +841,8 @@ int lifcal_init_plenoptic_recalibration(double fL_fixed, double B_fixed, lifcal_
 //   LIFCAL_GROUP_SPLIT   observations per lane above which a (point, frame) group is cut into several lanes (0 = never; default:
 //                        chosen per block by the planner's cost model)
 struct PlanChoice { bool use_sweep3 = true, use_sweep4 = false; int sweep_waves = 4, b4_tpt = 1; };
-static int plan_for_environment(const lifcal_ba_problem* p, int rank, int world, int deterministic, int precision, const lifcal_ba_partition* part, Plan* pl, PlanChoice* c) {
+static int plan_for_environment(const lifcal_ba_problem* p, int rank, int world, int deterministic, int precision, const lifcal_ba_partition* part, Plan* pl, PlanChoice* c,
+                                const std::vector<uint32_t>* prior_points = nullptr) {
   const bool enable_v2 = getenv("LIFCAL_DISABLE_V2") == nullptr;
   // the wave-specialised kernel wants the lanes of a pass sorted by frame, k_sweep2 (LIFCAL_SWEEP_KERNEL=2) by point
   int kernel = sweep_kernel_from_env();
@@ -852,7 +864,7 @@ static int plan_for_environment(const lifcal_ba_problem* p, int rank, int world,
   uint32_t plan_lanes, plan_blocks; sweep_layout(kernel, c->sweep_waves, &plan_lanes, &plan_blocks);
   const uint32_t v2_blocks = getenv("LIFCAL_V2_BLOCKS") ? (uint32_t)std::max(1, atoi(getenv("LIFCAL_V2_BLOCKS"))) : plan_blocks;
   const uint32_t split_obs = getenv("LIFCAL_GROUP_SPLIT") ? (uint32_t)std::max(0, atoi(getenv("LIFCAL_GROUP_SPLIT"))) : UINT32_MAX;
-  if (int rc = build_plan(p, rank, world, pl, enable_v2, v2_blocks, split_obs, c->use_sweep3, plan_lanes, precision == 1, part)) return rc;
+  if (int rc = build_plan(p, rank, world, pl, enable_v2, v2_blocks, split_obs, c->use_sweep3, plan_lanes, precision == 1, part, prior_points)) return rc;
   if (c->use_sweep4) {
     // k_back4 keeps at most two 4x4 tiles of the window per thread of a 256-thread group: wider frame windows take k_sweep3
     uint32_t max_ntri = 0;
@@ -861,7 +873,7 @@ static int plan_for_environment(const lifcal_ba_problem* p, int rank, int world,
       c->use_sweep4 = false; c->sweep_waves = 4;
       sweep_layout(3, 4, &plan_lanes, &plan_blocks);
       *pl = Plan();
-      if (int rc = build_plan(p, rank, world, pl, enable_v2, getenv("LIFCAL_V2_BLOCKS") ? v2_blocks : plan_blocks, split_obs, true, plan_lanes, false, part)) return rc;
+      if (int rc = build_plan(p, rank, world, pl, enable_v2, getenv("LIFCAL_V2_BLOCKS") ? v2_blocks : plan_blocks, split_obs, true, plan_lanes, false, part, prior_points)) return rc;
     } else {
       c->b4_tpt = max_ntri > 256 ? 2 : 1;
     }
@@ -902,9 +914,21 @@ int lifcal_ba_plan_shape(const lifcal_ba_problem* p, int32_t rank, int32_t world
   return 0;
 }
 
-static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, lifcal_ba_handle** out, const lifcal_ba_partition* part);
+static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, lifcal_ba_handle** out, const lifcal_ba_partition* part, const lifcal_ba_point_priors* pp = nullptr);
 
 int lifcal_ba_create(const lifcal_ba_problem* p, const lifcal_ba_options* o, lifcal_ba_handle** out) { return create_impl(p, o, out, nullptr); }
+
+int lifcal_ba_create_with_point_priors(const lifcal_ba_problem* p, const lifcal_ba_point_priors* pp, const lifcal_ba_options* o, lifcal_ba_handle** out) {
+  if (!pp || pp->n == 0) {   // exactly lifcal_ba_create; the (empty) point set is on record for lifcal_ba_set_point_priors
+    const int rc = create_impl(p, o, out, nullptr);
+    if (!rc) (*out)->pp_entry = true;
+    return rc;
+  }
+  if (!p || !out) return LIFCAL_BA_ERR_INVALID_ARG;
+  if (o && o->world_size > 1) { g_last_error = "lifcal_ba_create_with_point_priors: world_size > 1 is not supported (every rank would add the term)"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  if (int rc = lifcal_ba_check_point_priors(p->n_points, pp)) return rc;
+  return create_impl(p, o, out, nullptr, pp);
+}
 
 int lifcal_ba_create_shard(const lifcal_ba_problem* local, const lifcal_ba_partition* part, const lifcal_ba_options* o, lifcal_ba_handle** out) {
   if (!part) return LIFCAL_BA_ERR_INVALID_ARG;
@@ -921,7 +945,7 @@ int lifcal_ba_plan_shard(const lifcal_ba_problem* local, const lifcal_ba_partiti
   return 0;
 }
 
-static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, lifcal_ba_handle** out, const lifcal_ba_partition* part) {
+static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, lifcal_ba_handle** out, const lifcal_ba_partition* part, const lifcal_ba_point_priors* pp) {
   if (!out) return LIFCAL_BA_ERR_INVALID_ARG;
   *out = nullptr;
   lifcal_ba_options opt; if (o) opt = *o; else lifcal_ba_default_options(&opt);
@@ -938,7 +962,8 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
   {
     // tuning / A-B knobs (not part of the ABI) and the kernel fallbacks: plan_for_environment
     PlanChoice c;
-    const int rc = plan_for_environment(p, opt.rank, opt.world_size, opt.deterministic, opt.precision, part, &h->plan, &c);
+    if (pp) h->pp_point.assign(pp->point, pp->point + pp->n);   // (checked by the caller: ascending, below n_points)
+    const int rc = plan_for_environment(p, opt.rank, opt.world_size, opt.deterministic, opt.precision, part, &h->plan, &c, pp ? &h->pp_point : nullptr);
     if (rc) { delete h; return rc; }
     h->use_sweep3 = c.use_sweep3; h->use_sweep4 = c.use_sweep4; h->sweep_waves = c.sweep_waves; h->b4_tpt = c.b4_tpt;
   }
@@ -1153,6 +1178,11 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
       h->use_cr = true;
     }
   }
+  if (pp) {
+    A(h->pp_buf, 2 + 12 * (size_t)pp->n);
+    U(h->pp_point_dev, h->pp_point);
+    h->pp = PointPriorSet{pp->n, h->pp_point_dev, h->pp_buf + 2, h->pp_buf + 2 + 3 * (size_t)pp->n, d.ptacc};
+  }
 #undef A
 #undef U
   cclk.lap("create: alloc + upload");
@@ -1162,6 +1192,10 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
   if (hipHostGetDevicePointer((void**)&h->h_lm_dev, h->h_lm, 0) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP);
   if (int rc2 = upload_parameters(h)) return fail(rc2);
   cclk.lap("create: parameters");
+  if (pp) {
+    h->pp_entry = true;
+    if (int rc2 = lifcal_ba_set_point_priors(h, pp)) return fail(rc2);
+  }
   *out = h;
   return 0;
 }
@@ -1345,7 +1379,8 @@ int lifcal_ba_sweep(lifcal_ba_handle* h, double radius, lifcal_ba_sweep_out* out
     HIP_TRY(hipMemcpy(acc.data(), d.ptacc, acc.size() * 8, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(ui.data(), d.Uinv, ui.size() * 8, hipMemcpyDeviceToHost));
     for (uint32_t q = 0; q < d.P; ++q) {
-      const bool mine = d.use_points && h->plan.promoted[q] < 0 && h->plan.owner[q] == h->opt.rank && (h->plan.pt_nslots[q] > 0 || (h->plan.pt_cons0.size() > q + 1 && h->plan.pt_cons0[q + 1] > h->plan.pt_cons0[q]));
+      const bool mine = d.use_points && h->plan.promoted[q] < 0 && h->plan.owner[q] == h->opt.rank && (h->plan.pt_nslots[q] > 0 || (h->plan.pt_cons0.size() > q + 1 && h->plan.pt_cons0[q + 1] > h->plan.pt_cons0[q]) ||
+                         (h->pp_active && std::binary_search(h->pp_point.begin(), h->pp_point.end(), q)));   // (a prior alone makes the point a parameter)
       if (out->point_gradient) for (int k = 0; k < 3; ++k) out->point_gradient[3 * (size_t)q + k] = mine ? acc[(size_t)q * 36 + 6 + k] : 0.0;
       if (out->point_hessian_inv) for (int k = 0; k < 9; ++k) out->point_hessian_inv[9 * (size_t)q + k] = mine ? ui[(size_t)q * 9 + k] : 0.0;
     }
@@ -1398,7 +1433,8 @@ int lifcal_ba_debug_step(lifcal_ba_handle* h, lifcal_ba_step_out* out) {
     std::vector<double> dp(3 * (size_t)d.P);
     HIP_TRY(hipMemcpy(dp.data(), dev, dp.size() * 8, hipMemcpyDeviceToHost));
     for (uint32_t q = 0; q < d.P; ++q) {
-      const bool mine = h->plan.promoted[q] < 0 && h->plan.owner[q] == h->opt.rank && (h->plan.pt_nslots[q] > 0 || (h->plan.pt_cons0.size() > q + 1 && h->plan.pt_cons0[q + 1] > h->plan.pt_cons0[q]));
+      const bool mine = h->plan.promoted[q] < 0 && h->plan.owner[q] == h->opt.rank && (h->plan.pt_nslots[q] > 0 || (h->plan.pt_cons0.size() > q + 1 && h->plan.pt_cons0[q + 1] > h->plan.pt_cons0[q]) ||
+                         (h->pp_active && std::binary_search(h->pp_point.begin(), h->pp_point.end(), q)));   // (a prior alone makes the point a parameter)
       if (mine) for (int k = 0; k < 3; ++k) dst[3 * (size_t)q + k] = dp[3 * (size_t)q + k];
     }
     for (uint32_t qq = 0; qq < d.Q; ++qq) for (int k = 0; k < 3; ++k) dst[3 * (size_t)h->plan.promoted_ids[qq] + k] = red[F6 + 3 * qq + k];
@@ -1621,6 +1657,9 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 
 // covariance of the calibrated parameters: kernels and lifcal_ba_covariance (include/lifcal_ba.h)
 #include "covariance.hpp"
+
+// scene alignment onto control points: closed-form similarity and its application to poses and points (include/lifcal_align.h)
+#include "align.hpp"
 
 // residual report: per-observation errors and their sums by frame, point, lens or caller key (include/lifcal_ba.h)
 #include "residuals.hpp"

@@ -212,7 +212,8 @@ struct PlanClock {
 };
 
 inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl, bool enable_v2 = true, uint32_t target_blocks = 256, uint32_t split_obs = UINT32_MAX, bool frame_order = false,
-                      uint32_t pass_lanes = Plan::PASS_GROUPS, bool want_f32 = false, const lifcal_ba_partition* part = nullptr) {
+                      uint32_t pass_lanes = Plan::PASS_GROUPS, bool want_f32 = false, const lifcal_ba_partition* part = nullptr,
+                      const std::vector<uint32_t>* prior_points = nullptr) {
   PlanClock clk;
   if (int rc = plan_validate(p)) return rc;
   clk.lap("validate");
@@ -290,6 +291,8 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
     }
     for (uint32_t q = 0; q < L.P; ++q) if (flag[q]) { L.promoted[q] = (int32_t)L.promoted_ids.size(); L.promoted_ids.push_back(q); }
   }
+  // points with a Gaussian prior (lifcal_ba_create_with_point_priors) are parameters even without observations, as constraint points are
+  if (L.use_points && prior_points) for (uint32_t q : *prior_points) L.point_used[q] = 1;
   L.Q = (uint32_t)L.promoted_ids.size();
   L.NA = 3 * L.Q + (uint32_t)L.nc;
   L.n_red_int = 6 * L.F + L.NA;
@@ -493,6 +496,7 @@ inline int build_plan(const lifcal_ba_problem* p, int rank, int world, Plan* pl,
   // --- classify points: regular (v2) or special (v1 fallback) ---
   std::vector<uint8_t> special(L.P, 0);
   if (L.use_constraints) for (uint32_t c = 0; c < L.M; ++c) { special[L.c_i[c]] = 1; special[L.c_j[c]] = 1; }
+  if (L.use_points && prior_points) for (uint32_t q : *prior_points) special[q] = 1;   // k_point_priors adds into ptacc in front of k_schur
   for (uint32_t q = 0; q < L.P; ++q) {
     if (!cnt[q]) continue;
     if (!enable_v2 || !L.use_points) special[q] = 1;                    // camera-only / pose-only arities: v1 kernels

@@ -1,6 +1,6 @@
-// priors.hpp — Gaussian priors on the camera block and on poses (include/lifcal_prior.h): the kernel, its
-// launcher and the C ABI.  Included from lifcal_ba.hip behind the handle and in front of the launch helpers (launch_blocks and
-// launch_value_cost call launch_priors).
+// priors.hpp — Gaussian priors on the camera block and on poses (include/lifcal_prior.h) and on 3D points
+// (section 7r; k_point_priors itself lives in point_priors.hip): the kernels, their launchers and the C ABI.  Included from
+// lifcal_ba.hip behind the handle and in front of the launch helpers (launch_blocks and launch_value_cost call launch_priors).
 //
 // The term 1/2 d^T Lambda d, d = x - mean, touches reduced parameters only: it is added to the reduced block where k_constraints
 // adds the distance constraints, behind the sweep kernels on the stream, and to the value-only cost of a candidate.  The handle keeps
@@ -119,11 +119,22 @@ int launch_priors(lifcal_ba_handle* h, int cost_only, const double* cam, const d
   return 0;
 }
 
+// the point priors at `pts`: cost and blocks into the point slabs (in front of k_promote_diag / k_jacobi / k_schur), or (cost_only)
+// the cost alone, added to *out.  Nothing is launched without them
+int launch_point_priors(lifcal_ba_handle* h, int cost_only, const double* pts, double* out) {
+  if (!h->pp_active) return 0;
+  HIP_TRY(launch_k_point_priors(h->pp, cost_only, pts, out, h->stream));   // (point_priors.hip: a code object of its own)
+  return 0;
+}
+
 // rows the priors add to the residual vector as lifcal_ba_covariance counts it: one per live slot whose prior row is non-zero
 uint64_t prior_rows(const lifcal_ba_handle* h, const std::vector<uint8_t>& frame_live) {
-  if (!h->has_priors) return 0;
-  const Dev& d = h->d;
   uint64_t m = 0;
+  if (h->pp_active)
+    for (size_t k = 0; k < h->pp_point.size(); ++k)
+      for (uint32_t i = 0; i < 3; ++i) { const double* r = h->pp_info.data() + 9 * k + 3 * i; if (r[0] != 0.0 || r[1] != 0.0 || r[2] != 0.0) ++m; }
+  if (!h->has_priors) return m;
+  const Dev& d = h->d;
   auto nonzero_row = [](const double* A, uint32_t ld, uint32_t i, uint32_t n, auto&& live) { for (uint32_t j = 0; j < n; ++j) if (live(j) && A[i * ld + j] != 0.0) return true; return false; };
   if (!h->pr_cam_info.empty()) {
     auto live = [&](uint32_t j) { return !((d.fixed_mask >> j) & 1u); };
@@ -240,6 +251,63 @@ int lifcal_ba_prior_cost(lifcal_ba_handle* h, double* cam_cost, double* pose_cos
   }
   if (cam_cost) *cam_cost = c[0];
   if (pose_cost) *pose_cost = c[1];
+  return 0;
+}
+
+int lifcal_ba_check_point_priors(uint32_t n_points, const lifcal_ba_point_priors* p) {
+  if (!p) { g_last_error = "lifcal_ba_check_point_priors: null argument"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  if (p->n && (!p->point || !p->mean || !p->info)) { g_last_error = "lifcal_ba_check_point_priors: n > 0 with a null array"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  for (uint32_t k = 0; k < p->n; ++k) {
+    const std::string who = "lifcal_ba_check_point_priors: prior " + std::to_string(k) + ": ";
+    if (k && p->point[k] <= p->point[k - 1]) { g_last_error = who + "point ids are not strictly ascending"; return LIFCAL_BA_ERR_INVALID_ARG; }
+    for (int i = 0; i < 3; ++i) if (!std::isfinite(p->mean[3 * (size_t)k + i])) { g_last_error = who + "a non-finite mean"; return LIFCAL_BA_ERR_INVALID_ARG; }
+    if (const char* e = check_information(p->info + 9 * (size_t)k, 3)) { g_last_error = who + e; return LIFCAL_BA_ERR_INVALID_ARG; }
+  }
+  for (uint32_t k = 0; k < p->n; ++k)
+    if (p->point[k] >= n_points) { g_last_error = "lifcal_ba_check_point_priors: prior " + std::to_string(k) + ": point " + std::to_string(p->point[k]) + " of " + std::to_string(n_points); return LIFCAL_BA_ERR_OUT_OF_RANGE; }
+  return 0;
+}
+
+int lifcal_ba_set_point_priors(lifcal_ba_handle* h, const lifcal_ba_point_priors* p) {
+  if (!h) return LIFCAL_BA_ERR_INVALID_ARG;
+  if (!h->pp_entry) { g_last_error = "lifcal_ba_set_point_priors: the handle was not created by lifcal_ba_create_with_point_priors"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  const uint32_t n = (uint32_t)h->pp_point.size();
+  if (p) {
+    if (int rc = lifcal_ba_check_point_priors(h->d.P, p)) return rc;
+    if (p->n != n || !std::equal(h->pp_point.begin(), h->pp_point.end(), p->point)) {
+      g_last_error = "lifcal_ba_set_point_priors: the point set differs from the one given at create (the planner placed those points)"; return LIFCAL_BA_ERR_INVALID_ARG;
+    }
+  }
+  if (!n) return 0;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  HIP_TRY(hipStreamSynchronize(h->stream));   // a solve boundary, as lifcal_ba_set_priors
+  std::vector<double>& st = h->pp_stage;
+  st.assign(2 + 12 * (size_t)n, 0.0);
+  h->pp_info.assign(9 * (size_t)n, 0.0);
+  if (p) {
+    std::copy(p->mean, p->mean + 3 * (size_t)n, st.begin() + 2);
+    for (uint32_t k = 0; k < n; ++k)
+      for (int i = 0; i < 3; ++i) for (int j = 0; j < 3; ++j) h->pp_info[9 * (size_t)k + 3 * i + j] = 0.5 * (p->info[9 * (size_t)k + 3 * i + j] + p->info[9 * (size_t)k + 3 * j + i]);
+    std::copy(h->pp_info.begin(), h->pp_info.end(), st.begin() + 2 + 3 * (size_t)n);
+  }
+  HIP_TRY(hipMemcpyAsync(h->pp_buf, st.data(), st.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
+  // a problem that does not refine its points drops the term: the points are no parameters
+  h->pp_active = p != nullptr && h->d.use_points;
+  h->sigma_valid = false;   // the Hessian diagonal behind the Jacobi scaling changes: a new solve
+  h->swept = false;
+  return 0;
+}
+
+int lifcal_ba_point_prior_cost(lifcal_ba_handle* h, double* cost) {
+  if (!h || !cost) return LIFCAL_BA_ERR_INVALID_ARG;
+  *cost = 0.0;
+  if (!h->pp_active) return 0;
+  HIP_TRY(hipSetDevice(h->opt.device));
+  HIP_TRY(hipMemsetAsync(h->pp_buf, 0, sizeof(double), h->stream));
+  if (int rc = launch_point_priors(h, 1, h->d.pts, h->pp_buf)) return rc;
+  HIP_TRY(hipMemcpyAsync(cost, h->pp_buf, sizeof(double), hipMemcpyDeviceToHost, h->stream));
+  HIP_TRY(hipStreamSynchronize(h->stream));
   return 0;
 }
 

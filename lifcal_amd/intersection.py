@@ -43,6 +43,10 @@ class IntersectionResult:
     def g(self) -> np.ndarray:
         return self.rows["g"]
 
+    def point_information(self) -> np.ndarray:
+        """(P, 3, 3): H per point, the information matrix of a point prior (BundleAdjustment(..., point_priors=(ids, pts, infos)))."""
+        return self.H
+
     def _rms(self, name):
         n = self.rows["n_obs"].astype(np.float64)
         with np.errstate(divide="ignore", invalid="ignore"):
