@@ -280,27 +280,8 @@ __global__ __launch_bounds__(IS_THREADS, 3) void k_intersect(IntersectArgs a) {
 
 namespace {
 
-int intersect_checks(const lifcal_intersect_problem* p, const lifcal_ba_options* o, const lifcal_intersect_point* per_point) {
-  if (!p || !o || !per_point) { g_last_error = "lifcal_intersect_points: null problem, options or output rows"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (o->world_size > 1) { g_last_error = "lifcal_intersect_points: world_size > 1 is not supported"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (o->precision != 0) { g_last_error = "lifcal_intersect_points: options.precision must be 0"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (!p->cam || (p->n_frames && !p->views) || (p->n_points && !p->pts) ||
-      (p->n_obs && (!p->u || !p->v || !p->mcx || !p->mcy || !p->pt || !p->fr))) {
-    g_last_error = "lifcal_intersect_points: null array in the problem"; return LIFCAL_BA_ERR_INVALID_ARG;
-  }
-  if (p->n_obs > 0xFFFF0000u) { g_last_error = "lifcal_intersect_points: too many observations for 32-bit positions"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (p->n_points > 0xFFFF0000u) { g_last_error = "lifcal_intersect_points: too many points for 32-bit positions"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if ((p->config & LIFCAL_BA_CFG_NRADIAL_MASK) > 2u) { g_last_error = "lifcal_intersect_points: more than two radial coefficients"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  for (uint32_t i = 0; i < p->n_obs; ++i)
-    if (p->pt[i] >= p->n_points || p->fr[i] >= p->n_frames) {
-      g_last_error = "lifcal_intersect_points: observation " + std::to_string(i) + " names point " + std::to_string(p->pt[i]) + " / frame " + std::to_string(p->fr[i]) + " out of range";
-      return LIFCAL_BA_ERR_OUT_OF_RANGE;
-    }
-  return 0;
-}
-
 int intersect_impl(const lifcal_intersect_problem* p, const lifcal_ba_options* o, double inlier_threshold, lifcal_intersect_point* per_point, double* seconds) {
-  if (int rc = intersect_checks(p, o, per_point)) return rc;
+  if (int rc = batch_checks("lifcal_intersect_points", p, o, per_point, true)) return rc;
   if (seconds) *seconds = 0.0;
   const uint32_t N = p->n_obs, F = p->n_frames, P = p->n_points;
   if (!P) return 0;
@@ -308,42 +289,28 @@ int intersect_impl(const lifcal_intersect_problem* p, const lifcal_ba_options* o
   // the observations point-major, inside a point in the caller's order (stable counting sort)
   std::vector<uint32_t> off((size_t)P + 1), idx(N);
   if (int rc = lifcal_group_index(N, P, p->pt, off.data(), idx.data())) return rc;
-  ResectLayout L;
+  ByteLayout L;
   const size_t at_u = L.take((size_t)N * 8), at_v = L.take((size_t)N * 8), at_mx = L.take((size_t)N * 8), at_my = L.take((size_t)N * 8), at_fr = L.take((size_t)N * 4),
                at_off = L.take(((size_t)P + 1) * 4), at_cam = L.take(LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8), at_pts = L.take((size_t)P * 24), at_views = L.take((size_t)F * 48);
   const size_t in_bytes = L.bytes;
   const size_t at_cu = L.take((size_t)N * 16), at_cus = L.take((size_t)N * 16), at_camc = L.take(2 * sizeof(CamConsts)), at_ft = L.take((size_t)F * FRAME_STRIDE * 8),
                at_rows = L.take((size_t)P * sizeof(lifcal_intersect_point));
   std::vector<unsigned char> host(in_bytes);
-  {
-    double *hu = (double*)(host.data() + at_u), *hv = (double*)(host.data() + at_v), *hmx = (double*)(host.data() + at_mx), *hmy = (double*)(host.data() + at_my);
-    uint32_t* hfr = (uint32_t*)(host.data() + at_fr);
-    for (uint32_t k = 0; k < N; ++k) { const uint32_t i = idx[k]; hu[k] = p->u[i]; hv[k] = p->v[i]; hmx[k] = p->mcx[i]; hmy[k] = p->mcy[i]; hfr[k] = p->fr[i]; }
-    std::memcpy(host.data() + at_off, off.data(), off.size() * 4);
-    std::memcpy(host.data() + at_cam, p->cam, LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8);
-    std::memcpy(host.data() + at_pts, p->pts, (size_t)P * 24);
-    std::memcpy(host.data() + at_views, p->views, (size_t)F * 48);
-  }
+  stage_observations(host, idx, N, p, at_u, at_v, at_mx, at_my, at_fr, p->fr);
+  std::memcpy(host.data() + at_off, off.data(), off.size() * 4);
+  std::memcpy(host.data() + at_cam, p->cam, LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8);
+  std::memcpy(host.data() + at_pts, p->pts, (size_t)P * 24);
+  std::memcpy(host.data() + at_views, p->views, (size_t)F * 48);
 
   if (int rc = mla::select_device(o->device, "lifcal_intersect_points")) return rc;
-  hipStream_t stream = stream_pool_take(o->device);
-  unsigned char* dev = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  auto release = [&]() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (dev) (void)hipFree(dev);
-    if (stream && !stream_pool_give(o->device, stream)) (void)hipStreamDestroy(stream);
-  };
-  hipError_t err = hipSuccess;
-  if (!stream) err = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-  if (err == hipSuccess) err = hipMalloc((void**)&dev, L.bytes);
-  if (err == hipSuccess) err = hipEventCreate(&ev0);
-  if (err == hipSuccess) err = hipEventCreate(&ev1);
-  if (err == hipSuccess) err = hipMemcpyAsync(dev, host.data(), in_bytes, hipMemcpyHostToDevice, stream);
-  if (err == hipSuccess) err = hipMemsetAsync(dev + at_rows, 0, (size_t)P * sizeof(lifcal_intersect_point), stream);
-  if (err == hipSuccess) err = hipEventRecord(ev0, stream);
-  if (err == hipSuccess) {
+  BatchCall D(o->device, "lifcal_intersect_points");
+  D.open(L.bytes);
+  D.upload(host.data(), in_bytes);
+  D.zero(at_rows, (size_t)P * sizeof(lifcal_intersect_point));
+  D.begin();
+  if (D.ok()) {
+    unsigned char* const dev = D.dev;
+    hipStream_t const stream = D.stream;
     IntersectArgs a{};   // (the mask fields of the MASKED instantiations stay null)
     a.off = (const uint32_t*)(dev + at_off); a.fr = (const uint32_t*)(dev + at_fr);
     a.u = (const double*)(dev + at_u); a.v = (const double*)(dev + at_v); a.mcx = (const double*)(dev + at_mx); a.mcy = (const double*)(dev + at_my);
@@ -353,47 +320,24 @@ int intersect_impl(const lifcal_intersect_problem* p, const lifcal_ba_options* o
     a.lo = LmOpts{o->function_tolerance, o->parameter_tolerance, o->gradient_tolerance, o->min_relative_decrease, o->max_radius, o->min_radius, o->max_iterations};
     a.initial_radius = o->initial_radius; a.lm_min = o->min_lm_diagonal; a.lm_max = o->max_lm_diagonal; a.thr2 = inlier_threshold * inlier_threshold;
     a.n_points = P; a.robust = (p->config & LIFCAL_BA_CFG_ROBUST) ? 1u : 0u; a.jacobi = o->jacobi_scaling ? 1u : 0u;
-    const int nr = (int)(p->config & LIFCAL_BA_CFG_NRADIAL_MASK);
-    const bool tn = (p->config & LIFCAL_BA_CFG_TANGENTIAL) != 0, aj = (p->config & LIFCAL_BA_CFG_ML_CENTER_ADJ) != 0;
     const uint32_t lens_grid = (N + 255u) / 256u, frame_grid = (F + 255u) / 256u, point_grid = (P + (uint32_t)IS_WAVES - 1u) / (uint32_t)IS_WAVES;
-    // (the same dispatch tables as the handle's kernels, on the bits of the config instead of a plan)
-    struct { struct { int n_radial; bool tangential, adj; } plan; } cfg{{nr, tn, aj}};
-    auto launch = [&]() -> int {
-      hipLaunchKernelGGL(k_intersect_frames, dim3(frame_grid), dim3(256), 0, stream, (const double*)(dev + at_views), F, (double*)(dev + at_ft));
-#define CALL_RLENS(NR, TAN) do { \
-      hipLaunchKernelGGL((k_resect_lens<NR, TAN>), dim3(lens_grid), dim3(256), 0, stream, a.cam, p->spx, p->spy, p->scale, o->loss_scale, 1, N, a.mcx, a.mcy, (CamConsts*)(dev + at_camc), (double*)(dev + at_cu)); \
-      hipLaunchKernelGGL((k_resect_lens<NR, TAN>), dim3(lens_grid), dim3(256), 0, stream, a.cam, p->spx, p->spy, p->scale, o->loss_scale, 0, N, a.mcx, a.mcy, (CamConsts*)(dev + at_camc) + 1, (double*)(dev + at_cus)); } while (0)
-      DISPATCH_LENS(&cfg, CALL_RLENS);
-#undef CALL_RLENS
+    const ModelCfg cfg = model_cfg(p->config);
+    // (a dispatch table that refuses the configuration returns from here: D waits for the stream)
+    hipLaunchKernelGGL(k_intersect_frames, dim3(frame_grid), dim3(256), 0, stream, (const double*)(dev + at_views), F, (double*)(dev + at_ft));
+    for (int fold = 1; fold >= 0; --fold)
+      if (int rc = launch_lens_pass(cfg, stream, lens_grid, a.cam, p->spx, p->spy, p->scale, o->loss_scale, fold, N, a.mcx, a.mcy, (CamConsts*)(dev + at_camc), (double*)(dev + (fold ? at_cu : at_cus)))) return rc;
 #define CALL_INTERSECT(NR, TAN, ADJ) hipLaunchKernelGGL((k_intersect<NR, TAN, ADJ>), dim3(point_grid), dim3(IS_THREADS), 0, stream, a)
-      DISPATCH_CFG(&cfg, CALL_INTERSECT);
+    DISPATCH_CFG(&cfg, CALL_INTERSECT);
 #undef CALL_INTERSECT
-      return 0;
-    };
-    if (int rc = launch()) { (void)hipStreamSynchronize(stream); release(); return rc; }
-    err = hipGetLastError();
   }
-  if (err == hipSuccess) err = hipEventRecord(ev1, stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(p->pts, dev + at_pts, (size_t)P * 24, hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(per_point, dev + at_rows, (size_t)P * sizeof(lifcal_intersect_point), hipMemcpyDeviceToHost, stream);
-  const hipError_t es = stream ? hipStreamSynchronize(stream) : hipSuccess;   // (always: queued copies read host.data())
-  if (err == hipSuccess) err = es;
-  float ms = 0.f;
-  if (err == hipSuccess) err = hipEventElapsedTime(&ms, ev0, ev1);
-  release();
-  if (err != hipSuccess) { g_last_error = std::string("lifcal_intersect_points: ") + hipGetErrorString(err); return LIFCAL_BA_ERR_HIP; }
-  if (seconds) *seconds = 1e-3 * (double)ms;
-  return 0;
+  D.end();
+  D.download(p->pts, at_pts, (size_t)P * 24);
+  D.download(per_point, at_rows, (size_t)P * sizeof(lifcal_intersect_point));
+  return D.finish(seconds);
 }
 
 }  // namespace
 
 extern "C" int lifcal_intersect_points(const lifcal_intersect_problem* p, const lifcal_ba_options* o, double inlier_threshold, lifcal_intersect_point* per_point, double* seconds) {
-  try {   // (no exception crosses the C ABI)
-    return intersect_impl(p, o, inlier_threshold, per_point, seconds);
-  } catch (const std::bad_alloc&) {
-    g_last_error = "lifcal_intersect_points: out of host memory"; return LIFCAL_BA_ERR_NOMEM;
-  } catch (...) {
-    g_last_error = "lifcal_intersect_points: unexpected exception"; return LIFCAL_BA_ERR_INVALID_ARG;
-  }
+  return guard_abi("lifcal_intersect_points", [&] { return intersect_impl(p, o, inlier_threshold, per_point, seconds); });
 }

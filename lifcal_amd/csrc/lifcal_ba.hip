@@ -1670,6 +1670,9 @@ int lifcal_ba_project_observations(lifcal_ba_handle* h, double* x_proj, double* 
 // depth maps of several frames against each other: forward model, cross-view check, fusion (include/lifcal_depth.h (d)-(f))
 #include "depth_views.hpp"
 
+// the host side of the four files below: per-call driver, argument checks, staging, group building
+#include "batch_call.hpp"
+
 // batched pose resection of frames against a constant camera and constant points (include/lifcal_resect.h)
 #include "resection.hpp"
 

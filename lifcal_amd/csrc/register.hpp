@@ -205,7 +205,7 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
   if (!r || !per_point || !summary) { g_last_error = "lifcal_register_scene: null register options, point rows or summary"; return LIFCAL_BA_ERR_INVALID_ARG; }
   if (!(r->gate_px > 0.0)) { g_last_error = "lifcal_register_scene: gate_px must be > 0 (+infinity: no gate)"; return LIFCAL_BA_ERR_INVALID_ARG; }
   if (r->min_shared < 3u) { g_last_error = "lifcal_register_scene: min_shared must be >= 3"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (int rc = start_checks("lifcal_register_scene", p, o, per_frame)) return rc;
+  if (int rc = batch_checks("lifcal_register_scene", p, o, per_frame, true)) return rc;
   if (r->anchor_frame >= 0 && (uint32_t)r->anchor_frame >= p->n_frames) { g_last_error = "lifcal_register_scene: anchor_frame names no frame"; return LIFCAL_BA_ERR_INVALID_ARG; }
   const uint32_t N = p->n_obs, F = p->n_frames, P = p->n_points;
 
@@ -214,22 +214,13 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
   if (N) {
     if (int rc = lifcal_group_index(N, P, p->pt, poff.data(), pidx.data())) return rc;
     if (int rc = lifcal_group_index(N, F, p->fr, off.data(), fidx.data())) return rc;
-    std::vector<uint32_t> key2(N), idx2(N), off2((size_t)F + 1);
-    for (uint32_t k = 0; k < N; ++k) key2[k] = p->fr[pidx[k]];
-    if (int rc = lifcal_group_index(N, F, key2.data(), off2.data(), idx2.data())) return rc;
-    for (uint32_t k = 0; k < N; ++k) gidx[k] = pidx[idx2[k]];
+    if (int rc = frame_point_order(N, F, p->fr, pidx, off.data(), gidx)) return rc;   // (off once more: the same counts)
   }
   // the groups: runs of equal (fr, pt); per frame its run of groups, per point its groups in ascending frame order
-  std::vector<uint32_t> goff, gfr, gpt, fgoff((size_t)F + 1, 0u);
-  for (uint32_t k = 0; k < N; ++k) {
-    const uint32_t f = p->fr[gidx[k]], q = p->pt[gidx[k]];
-    if (k == 0 || f != gfr.back() || q != gpt.back()) { goff.push_back(k); gfr.push_back(f); gpt.push_back(q); ++fgoff[(size_t)f + 1]; }
-  }
-  goff.push_back(N);
-  const uint32_t G = (uint32_t)gfr.size();
-  for (uint32_t f = 0; f < F; ++f) fgoff[(size_t)f + 1] += fgoff[f];
+  const Groups g = build_groups(N, F, p->fr, p->pt, gidx);
+  const uint32_t G = g.G;
   std::vector<uint32_t> pgoff((size_t)P + 1, 0u), pgidx(G);
-  if (G) { if (int rc = lifcal_group_index(G, P, gpt.data(), pgoff.data(), pgidx.data())) return rc; }
+  if (G) { if (int rc = lifcal_group_index(G, P, g.gpt.data(), pgoff.data(), pgidx.data())) return rc; }
 
   // the rows every frame and point starts with
   std::vector<lifcal_register_frame> frows(F);
@@ -237,7 +228,7 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
   if (F) std::memset(frows.data(), 0, (size_t)F * sizeof(lifcal_register_frame));
   if (P) std::memset(prows.data(), 0, (size_t)P * sizeof(lifcal_register_point));
   for (uint32_t f = 0; f < F; ++f) {
-    frows[f].n_obs = off[(size_t)f + 1] - off[f]; frows[f].n_groups = fgoff[(size_t)f + 1] - fgoff[f]; frows[f].round = -1;
+    frows[f].n_obs = off[(size_t)f + 1] - off[f]; frows[f].n_groups = g.fgoff[(size_t)f + 1] - g.fgoff[f]; frows[f].round = -1;
     frows[f].status = frows[f].n_obs ? LIFCAL_REGISTER_FRAME_UNREACHED : LIFCAL_REGISTER_FRAME_EMPTY;
   }
   for (uint32_t k = 0; k < P; ++k) {
@@ -256,7 +247,7 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
   if (seconds) *seconds = 0.0;
   if (!N) return answer();   // nothing to register: no device is needed
 
-  ResectLayout L;
+  ByteLayout L;
   const size_t W = (size_t)N * 8;
   const size_t at_gu = L.take(W), at_gv = L.take(W), at_gmx = L.take(W), at_gmy = L.take(W),
                at_fu = L.take(W), at_fv = L.take(W), at_fmx = L.take(W), at_fmy = L.take(W), at_fpt = L.take((size_t)N * 4),
@@ -273,42 +264,32 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
   const size_t at_gcu = L.take((size_t)N * 16), at_fcu = L.take((size_t)N * 16), at_fcus = L.take((size_t)N * 16), at_pcu = L.take((size_t)N * 16), at_pcus = L.take((size_t)N * 16),
                at_camc = L.take(2 * sizeof(CamConsts)), at_grp = L.take((size_t)G * sizeof(lifcal_start_group));
   std::vector<unsigned char> host(in_bytes);
-  {
-    auto stage = [&](const std::vector<uint32_t>& idx, size_t au, size_t av, size_t amx, size_t amy, size_t akey, const uint32_t* key) {
-      double *hu = (double*)(host.data() + au), *hv = (double*)(host.data() + av), *hmx = (double*)(host.data() + amx), *hmy = (double*)(host.data() + amy);
-      uint32_t* hk = key ? (uint32_t*)(host.data() + akey) : nullptr;
-      for (uint32_t k = 0; k < N; ++k) { const uint32_t i = idx[k]; hu[k] = p->u[i]; hv[k] = p->v[i]; hmx[k] = p->mcx[i]; hmy[k] = p->mcy[i]; if (hk) hk[k] = key[i]; }
-    };
-    stage(gidx, at_gu, at_gv, at_gmx, at_gmy, 0, nullptr);
-    stage(fidx, at_fu, at_fv, at_fmx, at_fmy, at_fpt, p->pt);
-    stage(pidx, at_pu, at_pv, at_pmx, at_pmy, at_pfr, p->fr);
-    std::memcpy(host.data() + at_off, off.data(), off.size() * 4);
-    std::memcpy(host.data() + at_fgoff, fgoff.data(), fgoff.size() * 4);
-    std::memcpy(host.data() + at_poff, poff.data(), poff.size() * 4);
-    std::memcpy(host.data() + at_pgoff, pgoff.data(), pgoff.size() * 4);
-    std::memcpy(host.data() + at_pgidx, pgidx.data(), (size_t)G * 4);
-    std::memcpy(host.data() + at_goff, goff.data(), goff.size() * 4);
-    std::memcpy(host.data() + at_gfr, gfr.data(), (size_t)G * 4);
-    std::memcpy(host.data() + at_gpt, gpt.data(), (size_t)G * 4);
-    std::memcpy(host.data() + at_cam, p->cam, LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8);
-    std::memcpy(host.data() + at_frows, frows.data(), (size_t)F * sizeof(lifcal_register_frame));
-    std::memcpy(host.data() + at_prows, prows.data(), (size_t)P * sizeof(lifcal_register_point));
-  }
+  stage_observations(host, gidx, N, p, at_gu, at_gv, at_gmx, at_gmy, 0, nullptr);
+  stage_observations(host, fidx, N, p, at_fu, at_fv, at_fmx, at_fmy, at_fpt, p->pt);
+  stage_observations(host, pidx, N, p, at_pu, at_pv, at_pmx, at_pmy, at_pfr, p->fr);
+  std::memcpy(host.data() + at_off, off.data(), off.size() * 4);
+  std::memcpy(host.data() + at_fgoff, g.fgoff.data(), g.fgoff.size() * 4);
+  std::memcpy(host.data() + at_poff, poff.data(), poff.size() * 4);
+  std::memcpy(host.data() + at_pgoff, pgoff.data(), pgoff.size() * 4);
+  std::memcpy(host.data() + at_pgidx, pgidx.data(), (size_t)G * 4);
+  std::memcpy(host.data() + at_goff, g.goff.data(), g.goff.size() * 4);
+  std::memcpy(host.data() + at_gfr, g.gfr.data(), (size_t)G * 4);
+  std::memcpy(host.data() + at_gpt, g.gpt.data(), (size_t)G * 4);
+  std::memcpy(host.data() + at_cam, p->cam, LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8);
+  std::memcpy(host.data() + at_frows, frows.data(), (size_t)F * sizeof(lifcal_register_frame));
+  std::memcpy(host.data() + at_prows, prows.data(), (size_t)P * sizeof(lifcal_register_point));
   std::vector<double> views_out((size_t)F * 6), pts_out((size_t)P * 3);   // (p->views, p->pts are output only: nothing of them goes to the device)
 
   if (int rc = mla::select_device(o->device, "lifcal_register_scene")) return rc;
-  StartDevice D(o->device);
-  hipStream_t& stream = D.stream;
-  unsigned char*& dev = D.dev;
-  hipError_t err = D.open(L.bytes);
-  if (err == hipSuccess) err = hipMemcpyAsync(dev, host.data(), in_bytes, hipMemcpyHostToDevice, stream);
-  if (err == hipSuccess) err = hipMemsetAsync(dev + at_zero, 0, zero_bytes, stream);
-  if (err == hipSuccess) err = hipEventRecord(D.ev0, stream);
-  auto fail = [&](hipError_t e) {
-    if (stream) (void)hipStreamSynchronize(stream);   // (queued copies read host.data())
-    g_last_error = std::string("lifcal_register_scene: ") + hipGetErrorString(e); return LIFCAL_BA_ERR_HIP;
-  };
-  if (err != hipSuccess) return fail(err);
+  // (every return below leaves through D, which waits for the stream if anything is queued: the copies read and write the vectors above)
+  BatchCall D(o->device, "lifcal_register_scene");
+  D.open(L.bytes);
+  D.upload(host.data(), in_bytes);
+  D.zero(at_zero, zero_bytes);
+  D.begin();
+  if (!D.ok()) return D.fail();
+  unsigned char* const dev = D.dev;
+  hipStream_t const stream = D.stream;
 
   const double* d_cam = (const double*)(dev + at_cam);
   StartGroupArgs ga{};
@@ -343,18 +324,11 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
   ia.n_points = P; ia.robust = robust; ia.jacobi = jacobi;
   ia.fstate = a.fstate; ia.pmask = a.pmask; ia.reg_rows = a.prows;
 
-  const int nr = (int)(p->config & LIFCAL_BA_CFG_NRADIAL_MASK);
-  const bool tn = (p->config & LIFCAL_BA_CFG_TANGENTIAL) != 0, aj = (p->config & LIFCAL_BA_CFG_ML_CENTER_ADJ) != 0;
   const uint32_t lens_grid = (N + 255u) / 256u, group_grid = (G + (uint32_t)ST_THREADS - 1u) / (uint32_t)ST_THREADS, frame_grid = (F + 255u) / 256u,
                  point_grid = (P + (uint32_t)ST_WAVES - 1u) / (uint32_t)ST_WAVES, solve_grid = (P + (uint32_t)IS_WAVES - 1u) / (uint32_t)IS_WAVES;
-  // (the same dispatch tables as the handle's kernels, on the bits of the config instead of a plan)
-  struct { struct { int n_radial; bool tangential, adj; } plan; } cfg{{nr, tn, aj}};
+  const ModelCfg cfg = model_cfg(p->config);
   auto lens = [&](int fold, const double* mx, const double* my, size_t at_out) -> int {
-#define CALL_RLENS(NR, TAN) hipLaunchKernelGGL((k_resect_lens<NR, TAN>), dim3(lens_grid), dim3(256), 0, stream, d_cam, p->spx, p->spy, p->scale, o->loss_scale, fold, N, mx, my, \
-                                               (CamConsts*)(dev + at_camc) + (fold ? 0 : 1), (double*)(dev + at_out))
-    DISPATCH_LENS(&cfg, CALL_RLENS);
-#undef CALL_RLENS
-    return 0;
+    return launch_lens_pass(cfg, stream, lens_grid, d_cam, p->spx, p->spy, p->scale, o->loss_scale, fold, N, mx, my, (CamConsts*)(dev + at_camc), (double*)(dev + at_out));
   };
   auto groups = [&]() -> int {
 #define CALL_REG_GROUPS(NR, TAN, ADJ) hipLaunchKernelGGL((k_start_groups<NR, TAN, ADJ>), dim3(group_grid), dim3(ST_THREADS), 0, stream, ga)
@@ -388,7 +362,6 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
     hipLaunchKernelGGL(k_reg_extend, dim3(point_grid), dim3(ST_THREADS), 0, stream, a);
     return solve_points();
   };
-  auto bail = [&](int rc) { (void)hipStreamSynchronize(stream); return rc; };
 
   // the lens passes, the group table, the used groups of every frame -> the anchor
   int rc = lens(1, ga.mcx, ga.mcy, at_gcu);
@@ -397,12 +370,11 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
   if (!rc) rc = lens(1, a.pmx, a.pmy, at_pcu);
   if (!rc) rc = lens(0, a.pmx, a.pmy, at_pcus);
   if (!rc) rc = groups();
-  if (rc) return bail(rc);
+  if (rc) return rc;
   hipLaunchKernelGGL(k_reg_counts, dim3(F), dim3(ST_THREADS), 0, stream, a);
-  err = hipGetLastError();
-  if (err == hipSuccess) err = hipMemcpyAsync(frows.data(), dev + at_frows, (size_t)F * sizeof(lifcal_register_frame), hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(stream);
-  if (err != hipSuccess) return fail(err);
+  D.launched();
+  D.download(frows.data(), at_frows, (size_t)F * sizeof(lifcal_register_frame));
+  if ((rc = D.wait())) return rc;
   int64_t anchor = -1;
   for (uint32_t f = 0; f < F; ++f) {
     sum.n_groups_used += frows[f].n_used;
@@ -416,42 +388,36 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
   // round 0
   a.round = 0;
   hipLaunchKernelGGL(k_reg_anchor, dim3(1), dim3(64), 0, stream, a);
-  if ((rc = extend_and_refine_points())) return bail(rc);
+  if ((rc = extend_and_refine_points())) return rc;
   // rounds r >= 1: every round registers a frame or ends the loop
   for (uint32_t round = 1; round <= F && (r->max_rounds == 0 || round <= r->max_rounds); ++round) {
     a.round = (int32_t)round;
     hipLaunchKernelGGL(k_reg_frontier, dim3(F), dim3(ST_THREADS), 0, stream, a);
-    if ((rc = solve_poses(REG_NEW, 0xFFFFFFFFu))) return bail(rc);
+    if ((rc = solve_poses(REG_NEW, 0xFFFFFFFFu))) return rc;
     uint32_t n_new = 0;
-    err = hipGetLastError();
-    if (err == hipSuccess) err = hipMemcpyAsync(&n_new, dev + at_cnt + (size_t)round * 4, 4, hipMemcpyDeviceToHost, stream);
-    if (err == hipSuccess) err = hipStreamSynchronize(stream);
-    if (err != hipSuccess) return fail(err);
+    D.launched();
+    D.download(&n_new, at_cnt + (size_t)round * 4, 4);
+    if ((rc = D.wait())) return rc;
     if (!n_new) break;
     sum.n_rounds = round;
-    if ((rc = extend_and_refine_points())) return bail(rc);
-    if ((rc = solve_poses(REG_REGISTERED, a.anchor))) return bail(rc);
+    if ((rc = extend_and_refine_points())) return rc;
+    if ((rc = solve_poses(REG_REGISTERED, a.anchor))) return rc;
   }
   // the rows at the returned parameters; n_shared of the frames that were never aligned
   a.round = -1;
   hipLaunchKernelGGL(k_reg_frames, dim3(frame_grid), dim3(256), 0, stream, a);
   hipLaunchKernelGGL(k_reg_frontier, dim3(F), dim3(ST_THREADS), 0, stream, a);
-  if ((rc = stats())) return bail(rc);
-  err = hipGetLastError();
-  if (err == hipSuccess) err = hipEventRecord(D.ev1, stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(views_out.data(), dev + at_views, (size_t)F * 48, hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess && P) err = hipMemcpyAsync(pts_out.data(), dev + at_pts, (size_t)P * 24, hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(frows.data(), dev + at_frows, (size_t)F * sizeof(lifcal_register_frame), hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess && P) err = hipMemcpyAsync(prows.data(), dev + at_prows, (size_t)P * sizeof(lifcal_register_point), hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess) err = hipStreamSynchronize(stream);
-  float ms = 0.f;
-  if (err == hipSuccess) err = hipEventElapsedTime(&ms, D.ev0, D.ev1);
-  if (err != hipSuccess) return fail(err);
+  if ((rc = stats())) return rc;
+  D.end();
+  D.download(views_out.data(), at_views, (size_t)F * 48);
+  if (P) D.download(pts_out.data(), at_pts, (size_t)P * 24);
+  D.download(frows.data(), at_frows, (size_t)F * sizeof(lifcal_register_frame));
+  if (P) D.download(prows.data(), at_prows, (size_t)P * sizeof(lifcal_register_point));
+  if ((rc = D.finish(seconds))) return rc;
   for (uint32_t f = 0; f < F; ++f)
     if (frows[f].status == LIFCAL_REGISTER_FRAME_OK) { std::memcpy(p->views + 6 * (size_t)f, views_out.data() + 6 * (size_t)f, 48); ++sum.n_frames_registered; }
   for (uint32_t k = 0; k < P; ++k)
     if (prows[k].status == LIFCAL_REGISTER_POINT_OK) { std::memcpy(p->pts + 3 * (size_t)k, pts_out.data() + 3 * (size_t)k, 24); ++sum.n_points_mapped; }
-  if (seconds) *seconds = 1e-3 * (double)ms;
   return answer();
 }
 
@@ -459,11 +425,5 @@ int register_impl(const lifcal_register_problem* p, const lifcal_ba_options* o, 
 
 extern "C" int lifcal_register_scene(const lifcal_register_problem* p, const lifcal_ba_options* o, const lifcal_register_options* r,
                                      lifcal_register_frame* per_frame, lifcal_register_point* per_point, lifcal_register_summary* summary, double* seconds) {
-  try {   // (no exception crosses the C ABI)
-    return register_impl(p, o, r, per_frame, per_point, summary, seconds);
-  } catch (const std::bad_alloc&) {
-    g_last_error = "lifcal_register_scene: out of host memory"; return LIFCAL_BA_ERR_NOMEM;
-  } catch (...) {
-    g_last_error = "lifcal_register_scene: unexpected exception"; return LIFCAL_BA_ERR_INVALID_ARG;
-  }
+  return guard_abi("lifcal_register_scene", [&] { return register_impl(p, o, r, per_frame, per_point, summary, seconds); });
 }

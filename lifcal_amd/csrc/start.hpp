@@ -1,6 +1,6 @@
 // start.hpp — lifcal_start_poses and lifcal_start_points (include/lifcal_start.h): closed-form start values from micro-image
 // rays.  Its kernels, then the host drivers (included at the end of lifcal_ba.hip, behind resection.hpp and intersection.hpp,
-// whose k_resect_lens, rs_fold, k_intersect_frames and ResectLayout it reuses).  DESIGN.md section 7n.
+// whose k_resect_lens, rs_fold and k_intersect_frames it reuses).  DESIGN.md section 7n.
 //
 //   k_resect_lens    (resection.hpp) c_u of every observation and the camera constants, folded | as stored
 //   start_ray        the two rows of one observation: linear in the camera-frame point once (u, v) is given
@@ -441,54 +441,9 @@ __global__ __launch_bounds__(ST_THREADS) void k_start_points(StartPointArgs a) {
 
 namespace {
 
-// the argument checks the two entry points share (the problem structs name their fields alike)
-template <class Problem>
-int start_checks(const char* fn, const Problem* p, const lifcal_ba_options* o, const void* rows) {
-  const std::string name(fn);
-  if (!p || !o || !rows) { g_last_error = name + ": null problem, options or output rows"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (o->world_size > 1) { g_last_error = name + ": world_size > 1 is not supported"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (o->precision != 0) { g_last_error = name + ": options.precision must be 0"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (!p->cam || (p->n_frames && !p->views) || (p->n_points && !p->pts) ||
-      (p->n_obs && (!p->u || !p->v || !p->mcx || !p->mcy || !p->pt || !p->fr))) {
-    g_last_error = name + ": null array in the problem"; return LIFCAL_BA_ERR_INVALID_ARG;
-  }
-  if (p->n_obs > 0xFFFF0000u) { g_last_error = name + ": too many observations for 32-bit positions"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (p->n_points > 0xFFFF0000u) { g_last_error = name + ": too many points for 32-bit positions"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if ((p->config & LIFCAL_BA_CFG_NRADIAL_MASK) > 2u) { g_last_error = name + ": more than two radial coefficients"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  for (uint32_t i = 0; i < p->n_obs; ++i)
-    if (p->pt[i] >= p->n_points || p->fr[i] >= p->n_frames) {
-      g_last_error = name + ": observation " + std::to_string(i) + " names point " + std::to_string(p->pt[i]) + " / frame " + std::to_string(p->fr[i]) + " out of range";
-      return LIFCAL_BA_ERR_OUT_OF_RANGE;
-    }
-  return 0;
-}
-
-// stream, device block and events of one call; released on every way out
-struct StartDevice {
-  int device;
-  hipStream_t stream = nullptr;
-  unsigned char* dev = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  explicit StartDevice(int d) : device(d), stream(stream_pool_take(d)) {}
-  hipError_t open(size_t bytes) {
-    hipError_t err = hipSuccess;
-    if (!stream) err = hipStreamCreateWithFlags(&stream, hipStreamNonBlocking);
-    if (err == hipSuccess) err = hipMalloc((void**)&dev, bytes);
-    if (err == hipSuccess) err = hipEventCreate(&ev0);
-    if (err == hipSuccess) err = hipEventCreate(&ev1);
-    return err;
-  }
-  ~StartDevice() {
-    if (ev0) (void)hipEventDestroy(ev0);
-    if (ev1) (void)hipEventDestroy(ev1);
-    if (dev) (void)hipFree(dev);
-    if (stream && !stream_pool_give(device, stream)) (void)hipStreamDestroy(stream);
-  }
-};
-
 int start_poses_impl(const lifcal_resect_problem* p, const lifcal_ba_options* o, double gate_px, double inlier_threshold,
                      lifcal_start_frame* per_frame, lifcal_start_group* groups, uint32_t* n_groups, double* seconds) {
-  if (int rc = start_checks("lifcal_start_poses", p, o, per_frame)) return rc;
+  if (int rc = batch_checks("lifcal_start_poses", p, o, per_frame, true)) return rc;
   if (!(gate_px > 0.0)) { g_last_error = "lifcal_start_poses: gate_px must be > 0 (+infinity: no gate)"; return LIFCAL_BA_ERR_INVALID_ARG; }
   if (seconds) *seconds = 0.0;
   if (n_groups) *n_groups = 0;
@@ -499,26 +454,16 @@ int start_poses_impl(const lifcal_resect_problem* p, const lifcal_ba_options* o,
     for (uint32_t f = 0; f < F; ++f) per_frame[f].status = LIFCAL_START_FRAME_EMPTY;
     return 0;
   }
-  // the observations (fr, pt)-major, inside a group in the caller's order: two stable counting sorts, by pt, then by fr
   std::vector<uint32_t> off((size_t)F + 1), idx(N);
   {
-    std::vector<uint32_t> offp((size_t)P + 1), idx1(N), key2(N), idx2(N);
-    if (int rc = lifcal_group_index(N, P, p->pt, offp.data(), idx1.data())) return rc;
-    for (uint32_t k = 0; k < N; ++k) key2[k] = p->fr[idx1[k]];
-    if (int rc = lifcal_group_index(N, F, key2.data(), off.data(), idx2.data())) return rc;
-    for (uint32_t k = 0; k < N; ++k) idx[k] = idx1[idx2[k]];
+    std::vector<uint32_t> offp((size_t)P + 1), pidx(N);
+    if (int rc = lifcal_group_index(N, P, p->pt, offp.data(), pidx.data())) return rc;
+    if (int rc = frame_point_order(N, F, p->fr, pidx, off.data(), idx)) return rc;
   }
-  // the groups: runs of equal (fr, pt); per frame its run of groups
-  std::vector<uint32_t> goff, gfr, gpt, fgoff((size_t)F + 1, 0u);
-  for (uint32_t k = 0; k < N; ++k) {
-    const uint32_t f = p->fr[idx[k]], q = p->pt[idx[k]];
-    if (k == 0 || f != gfr.back() || q != gpt.back()) { goff.push_back(k); gfr.push_back(f); gpt.push_back(q); ++fgoff[(size_t)f + 1]; }
-  }
-  goff.push_back(N);
-  const uint32_t G = (uint32_t)gfr.size();
-  for (uint32_t f = 0; f < F; ++f) fgoff[(size_t)f + 1] += fgoff[f];
+  const Groups g = build_groups(N, F, p->fr, p->pt, idx);
+  const uint32_t G = g.G;
 
-  ResectLayout L;
+  ByteLayout L;
   const size_t at_u = L.take((size_t)N * 8), at_v = L.take((size_t)N * 8), at_mx = L.take((size_t)N * 8), at_my = L.take((size_t)N * 8), at_pt = L.take((size_t)N * 4),
                at_off = L.take(((size_t)F + 1) * 4), at_fgoff = L.take(((size_t)F + 1) * 4), at_goff = L.take(((size_t)G + 1) * 4), at_gfr = L.take((size_t)G * 4),
                at_gpt = L.take((size_t)G * 4), at_cam = L.take(LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8), at_pts = L.take((size_t)P * 24);
@@ -526,30 +471,26 @@ int start_poses_impl(const lifcal_resect_problem* p, const lifcal_ba_options* o,
   const size_t at_cu = L.take((size_t)N * 16), at_cus = L.take((size_t)N * 16), at_camc = L.take(2 * sizeof(CamConsts)), at_grp = L.take((size_t)G * sizeof(lifcal_start_group)),
                at_views = L.take((size_t)F * 48), at_rows = L.take((size_t)F * sizeof(lifcal_start_frame));
   std::vector<unsigned char> host(in_bytes);
-  {
-    double *hu = (double*)(host.data() + at_u), *hv = (double*)(host.data() + at_v), *hmx = (double*)(host.data() + at_mx), *hmy = (double*)(host.data() + at_my);
-    uint32_t* hpt = (uint32_t*)(host.data() + at_pt);
-    for (uint32_t k = 0; k < N; ++k) { const uint32_t i = idx[k]; hu[k] = p->u[i]; hv[k] = p->v[i]; hmx[k] = p->mcx[i]; hmy[k] = p->mcy[i]; hpt[k] = p->pt[i]; }
-    std::memcpy(host.data() + at_off, off.data(), off.size() * 4);
-    std::memcpy(host.data() + at_fgoff, fgoff.data(), fgoff.size() * 4);
-    std::memcpy(host.data() + at_goff, goff.data(), goff.size() * 4);
-    std::memcpy(host.data() + at_gfr, gfr.data(), (size_t)G * 4);
-    std::memcpy(host.data() + at_gpt, gpt.data(), (size_t)G * 4);
-    std::memcpy(host.data() + at_cam, p->cam, LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8);
-    std::memcpy(host.data() + at_pts, p->pts, (size_t)P * 24);
-  }
+  stage_observations(host, idx, N, p, at_u, at_v, at_mx, at_my, at_pt, p->pt);
+  std::memcpy(host.data() + at_off, off.data(), off.size() * 4);
+  std::memcpy(host.data() + at_fgoff, g.fgoff.data(), g.fgoff.size() * 4);
+  std::memcpy(host.data() + at_goff, g.goff.data(), g.goff.size() * 4);
+  std::memcpy(host.data() + at_gfr, g.gfr.data(), (size_t)G * 4);
+  std::memcpy(host.data() + at_gpt, g.gpt.data(), (size_t)G * 4);
+  std::memcpy(host.data() + at_cam, p->cam, LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8);
+  std::memcpy(host.data() + at_pts, p->pts, (size_t)P * 24);
   std::vector<double> views_out((size_t)F * 6);   // (p->views is output only: nothing of it goes to the device)
 
   if (int rc = mla::select_device(o->device, "lifcal_start_poses")) return rc;
-  StartDevice D(o->device);
-  hipStream_t& stream = D.stream;
-  unsigned char*& dev = D.dev;
-  hipError_t err = D.open(L.bytes);
-  if (err == hipSuccess) err = hipMemcpyAsync(dev, host.data(), in_bytes, hipMemcpyHostToDevice, stream);
-  if (err == hipSuccess) err = hipMemsetAsync(dev + at_views, 0, (size_t)F * 48, stream);
-  if (err == hipSuccess) err = hipMemsetAsync(dev + at_rows, 0, (size_t)F * sizeof(lifcal_start_frame), stream);
-  if (err == hipSuccess) err = hipEventRecord(D.ev0, stream);
-  if (err == hipSuccess) {
+  BatchCall D(o->device, "lifcal_start_poses");
+  D.open(L.bytes);
+  D.upload(host.data(), in_bytes);
+  D.zero(at_views, (size_t)F * 48);
+  D.zero(at_rows, (size_t)F * sizeof(lifcal_start_frame));
+  D.begin();
+  if (D.ok()) {
+    unsigned char* const dev = D.dev;
+    hipStream_t const stream = D.stream;
     const double* d_cam = (const double*)(dev + at_cam);
     StartGroupArgs ga;
     ga.goff = (const uint32_t*)(dev + at_goff); ga.gfr = (const uint32_t*)(dev + at_gfr); ga.gpt = (const uint32_t*)(dev + at_gpt);
@@ -561,45 +502,30 @@ int start_poses_impl(const lifcal_resect_problem* p, const lifcal_ba_options* o,
     aa.u = ga.u; aa.v = ga.v; aa.mcx = ga.mcx; aa.mcy = ga.mcy; aa.cu_stats = (const double*)(dev + at_cus); aa.camc = ga.camc;
     aa.pts = (const double*)(dev + at_pts); aa.groups = ga.groups; aa.views = (double*)(dev + at_views); aa.rows = (lifcal_start_frame*)(dev + at_rows);
     aa.thr2 = inlier_threshold * inlier_threshold;
-    const int nr = (int)(p->config & LIFCAL_BA_CFG_NRADIAL_MASK);
-    const bool tn = (p->config & LIFCAL_BA_CFG_TANGENTIAL) != 0, aj = (p->config & LIFCAL_BA_CFG_ML_CENTER_ADJ) != 0;
     const uint32_t lens_grid = (N + 255u) / 256u, group_grid = (G + (uint32_t)ST_THREADS - 1u) / (uint32_t)ST_THREADS;
-    // (the same dispatch tables as the handle's kernels, on the bits of the config instead of a plan)
-    struct { struct { int n_radial; bool tangential, adj; } plan; } cfg{{nr, tn, aj}};
-    auto launch = [&]() -> int {
-#define CALL_RLENS(NR, TAN) do { \
-      hipLaunchKernelGGL((k_resect_lens<NR, TAN>), dim3(lens_grid), dim3(256), 0, stream, d_cam, p->spx, p->spy, p->scale, o->loss_scale, 1, N, ga.mcx, ga.mcy, (CamConsts*)(dev + at_camc), (double*)(dev + at_cu)); \
-      hipLaunchKernelGGL((k_resect_lens<NR, TAN>), dim3(lens_grid), dim3(256), 0, stream, d_cam, p->spx, p->spy, p->scale, o->loss_scale, 0, N, ga.mcx, ga.mcy, (CamConsts*)(dev + at_camc) + 1, (double*)(dev + at_cus)); } while (0)
-      DISPATCH_LENS(&cfg, CALL_RLENS);
-#undef CALL_RLENS
+    const ModelCfg cfg = model_cfg(p->config);
+    // (a dispatch table that refuses the configuration returns from here: D waits for the stream)
+    for (int fold = 1; fold >= 0; --fold)
+      if (int rc = launch_lens_pass(cfg, stream, lens_grid, d_cam, p->spx, p->spy, p->scale, o->loss_scale, fold, N, ga.mcx, ga.mcy, (CamConsts*)(dev + at_camc), (double*)(dev + (fold ? at_cu : at_cus)))) return rc;
 #define CALL_START_POSES(NR, TAN, ADJ) do { \
-      hipLaunchKernelGGL((k_start_groups<NR, TAN, ADJ>), dim3(group_grid), dim3(ST_THREADS), 0, stream, ga); \
-      hipLaunchKernelGGL((k_start_align<NR, TAN, ADJ>), dim3(F), dim3(ST_THREADS), 0, stream, aa); } while (0)
-      DISPATCH_CFG(&cfg, CALL_START_POSES);
+    hipLaunchKernelGGL((k_start_groups<NR, TAN, ADJ>), dim3(group_grid), dim3(ST_THREADS), 0, stream, ga); \
+    hipLaunchKernelGGL((k_start_align<NR, TAN, ADJ>), dim3(F), dim3(ST_THREADS), 0, stream, aa); } while (0)
+    DISPATCH_CFG(&cfg, CALL_START_POSES);
 #undef CALL_START_POSES
-      return 0;
-    };
-    if (int rc = launch()) { (void)hipStreamSynchronize(stream); return rc; }
-    err = hipGetLastError();
   }
-  if (err == hipSuccess) err = hipEventRecord(D.ev1, stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(views_out.data(), dev + at_views, (size_t)F * 48, hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(per_frame, dev + at_rows, (size_t)F * sizeof(lifcal_start_frame), hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess && groups) err = hipMemcpyAsync(groups, dev + at_grp, (size_t)G * sizeof(lifcal_start_group), hipMemcpyDeviceToHost, stream);
-  const hipError_t es = stream ? hipStreamSynchronize(stream) : hipSuccess;   // (always: queued copies read host.data())
-  if (err == hipSuccess) err = es;
-  float ms = 0.f;
-  if (err == hipSuccess) err = hipEventElapsedTime(&ms, D.ev0, D.ev1);
-  if (err != hipSuccess) { g_last_error = std::string("lifcal_start_poses: ") + hipGetErrorString(err); return LIFCAL_BA_ERR_HIP; }
+  D.end();
+  D.download(views_out.data(), at_views, (size_t)F * 48);
+  D.download(per_frame, at_rows, (size_t)F * sizeof(lifcal_start_frame));
+  if (groups) D.download(groups, at_grp, (size_t)G * sizeof(lifcal_start_group));
+  if (int rc = D.finish(seconds)) return rc;
   for (uint32_t f = 0; f < F; ++f)
     if (per_frame[f].status == LIFCAL_START_FRAME_OK) std::memcpy(p->views + 6 * (size_t)f, views_out.data() + 6 * (size_t)f, 48);
   if (n_groups) *n_groups = G;
-  if (seconds) *seconds = 1e-3 * (double)ms;
   return 0;
 }
 
 int start_points_impl(const lifcal_intersect_problem* p, const lifcal_ba_options* o, double inlier_threshold, lifcal_start_point* per_point, double* seconds) {
-  if (int rc = start_checks("lifcal_start_points", p, o, per_point)) return rc;
+  if (int rc = batch_checks("lifcal_start_points", p, o, per_point, true)) return rc;
   if (seconds) *seconds = 0.0;
   const uint32_t N = p->n_obs, F = p->n_frames, P = p->n_points;
   if (!P) return 0;
@@ -611,33 +537,29 @@ int start_points_impl(const lifcal_intersect_problem* p, const lifcal_ba_options
   // the observations point-major, inside a point in the caller's order (stable counting sort)
   std::vector<uint32_t> off((size_t)P + 1), idx(N);
   if (int rc = lifcal_group_index(N, P, p->pt, off.data(), idx.data())) return rc;
-  ResectLayout L;
+  ByteLayout L;
   const size_t at_u = L.take((size_t)N * 8), at_v = L.take((size_t)N * 8), at_mx = L.take((size_t)N * 8), at_my = L.take((size_t)N * 8), at_fr = L.take((size_t)N * 4),
                at_off = L.take(((size_t)P + 1) * 4), at_cam = L.take(LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8), at_views = L.take((size_t)F * 48);
   const size_t in_bytes = L.bytes;
   const size_t at_cu = L.take((size_t)N * 16), at_cus = L.take((size_t)N * 16), at_camc = L.take(2 * sizeof(CamConsts)), at_ft = L.take((size_t)F * FRAME_STRIDE * 8),
                at_pts = L.take((size_t)P * 24), at_rows = L.take((size_t)P * sizeof(lifcal_start_point));
   std::vector<unsigned char> host(in_bytes);
-  {
-    double *hu = (double*)(host.data() + at_u), *hv = (double*)(host.data() + at_v), *hmx = (double*)(host.data() + at_mx), *hmy = (double*)(host.data() + at_my);
-    uint32_t* hfr = (uint32_t*)(host.data() + at_fr);
-    for (uint32_t k = 0; k < N; ++k) { const uint32_t i = idx[k]; hu[k] = p->u[i]; hv[k] = p->v[i]; hmx[k] = p->mcx[i]; hmy[k] = p->mcy[i]; hfr[k] = p->fr[i]; }
-    std::memcpy(host.data() + at_off, off.data(), off.size() * 4);
-    std::memcpy(host.data() + at_cam, p->cam, LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8);
-    std::memcpy(host.data() + at_views, p->views, (size_t)F * 48);
-  }
+  stage_observations(host, idx, N, p, at_u, at_v, at_mx, at_my, at_fr, p->fr);
+  std::memcpy(host.data() + at_off, off.data(), off.size() * 4);
+  std::memcpy(host.data() + at_cam, p->cam, LIFCAL_BA_MAX_CAMERA_PARAMETERS * 8);
+  std::memcpy(host.data() + at_views, p->views, (size_t)F * 48);
   std::vector<double> pts_out((size_t)P * 3);   // (p->pts is output only: nothing of it goes to the device)
 
   if (int rc = mla::select_device(o->device, "lifcal_start_points")) return rc;
-  StartDevice D(o->device);
-  hipStream_t& stream = D.stream;
-  unsigned char*& dev = D.dev;
-  hipError_t err = D.open(L.bytes);
-  if (err == hipSuccess) err = hipMemcpyAsync(dev, host.data(), in_bytes, hipMemcpyHostToDevice, stream);
-  if (err == hipSuccess) err = hipMemsetAsync(dev + at_pts, 0, (size_t)P * 24, stream);
-  if (err == hipSuccess) err = hipMemsetAsync(dev + at_rows, 0, (size_t)P * sizeof(lifcal_start_point), stream);
-  if (err == hipSuccess) err = hipEventRecord(D.ev0, stream);
-  if (err == hipSuccess) {
+  BatchCall D(o->device, "lifcal_start_points");
+  D.open(L.bytes);
+  D.upload(host.data(), in_bytes);
+  D.zero(at_pts, (size_t)P * 24);
+  D.zero(at_rows, (size_t)P * sizeof(lifcal_start_point));
+  D.begin();
+  if (D.ok()) {
+    unsigned char* const dev = D.dev;
+    hipStream_t const stream = D.stream;
     const double* d_cam = (const double*)(dev + at_cam);
     StartPointArgs a;
     a.off = (const uint32_t*)(dev + at_off); a.fr = (const uint32_t*)(dev + at_fr);
@@ -645,36 +567,22 @@ int start_points_impl(const lifcal_intersect_problem* p, const lifcal_ba_options
     a.cu = (const double*)(dev + at_cu); a.cu_stats = (const double*)(dev + at_cus); a.camc = (const CamConsts*)(dev + at_camc);
     a.ft = (const double*)(dev + at_ft); a.pts = (double*)(dev + at_pts); a.rows = (lifcal_start_point*)(dev + at_rows);
     a.thr2 = inlier_threshold * inlier_threshold; a.n_points = P;
-    const int nr = (int)(p->config & LIFCAL_BA_CFG_NRADIAL_MASK);
-    const bool tn = (p->config & LIFCAL_BA_CFG_TANGENTIAL) != 0, aj = (p->config & LIFCAL_BA_CFG_ML_CENTER_ADJ) != 0;
     const uint32_t lens_grid = (N + 255u) / 256u, frame_grid = (F + 255u) / 256u, point_grid = (P + (uint32_t)ST_WAVES - 1u) / (uint32_t)ST_WAVES;
-    struct { struct { int n_radial; bool tangential, adj; } plan; } cfg{{nr, tn, aj}};
-    auto launch = [&]() -> int {
-      hipLaunchKernelGGL(k_intersect_frames, dim3(frame_grid), dim3(256), 0, stream, (const double*)(dev + at_views), F, (double*)(dev + at_ft));
-#define CALL_RLENS(NR, TAN) do { \
-      hipLaunchKernelGGL((k_resect_lens<NR, TAN>), dim3(lens_grid), dim3(256), 0, stream, d_cam, p->spx, p->spy, p->scale, o->loss_scale, 1, N, a.mcx, a.mcy, (CamConsts*)(dev + at_camc), (double*)(dev + at_cu)); \
-      hipLaunchKernelGGL((k_resect_lens<NR, TAN>), dim3(lens_grid), dim3(256), 0, stream, d_cam, p->spx, p->spy, p->scale, o->loss_scale, 0, N, a.mcx, a.mcy, (CamConsts*)(dev + at_camc) + 1, (double*)(dev + at_cus)); } while (0)
-      DISPATCH_LENS(&cfg, CALL_RLENS);
-#undef CALL_RLENS
+    const ModelCfg cfg = model_cfg(p->config);
+    // (a dispatch table that refuses the configuration returns from here: D waits for the stream)
+    hipLaunchKernelGGL(k_intersect_frames, dim3(frame_grid), dim3(256), 0, stream, (const double*)(dev + at_views), F, (double*)(dev + at_ft));
+    for (int fold = 1; fold >= 0; --fold)
+      if (int rc = launch_lens_pass(cfg, stream, lens_grid, d_cam, p->spx, p->spy, p->scale, o->loss_scale, fold, N, a.mcx, a.mcy, (CamConsts*)(dev + at_camc), (double*)(dev + (fold ? at_cu : at_cus)))) return rc;
 #define CALL_START_POINTS(NR, TAN, ADJ) hipLaunchKernelGGL((k_start_points<NR, TAN, ADJ>), dim3(point_grid), dim3(ST_THREADS), 0, stream, a)
-      DISPATCH_CFG(&cfg, CALL_START_POINTS);
+    DISPATCH_CFG(&cfg, CALL_START_POINTS);
 #undef CALL_START_POINTS
-      return 0;
-    };
-    if (int rc = launch()) { (void)hipStreamSynchronize(stream); return rc; }
-    err = hipGetLastError();
   }
-  if (err == hipSuccess) err = hipEventRecord(D.ev1, stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(pts_out.data(), dev + at_pts, (size_t)P * 24, hipMemcpyDeviceToHost, stream);
-  if (err == hipSuccess) err = hipMemcpyAsync(per_point, dev + at_rows, (size_t)P * sizeof(lifcal_start_point), hipMemcpyDeviceToHost, stream);
-  const hipError_t es = stream ? hipStreamSynchronize(stream) : hipSuccess;   // (always: queued copies read host.data())
-  if (err == hipSuccess) err = es;
-  float ms = 0.f;
-  if (err == hipSuccess) err = hipEventElapsedTime(&ms, D.ev0, D.ev1);
-  if (err != hipSuccess) { g_last_error = std::string("lifcal_start_points: ") + hipGetErrorString(err); return LIFCAL_BA_ERR_HIP; }
+  D.end();
+  D.download(pts_out.data(), at_pts, (size_t)P * 24);
+  D.download(per_point, at_rows, (size_t)P * sizeof(lifcal_start_point));
+  if (int rc = D.finish(seconds)) return rc;
   for (uint32_t k = 0; k < P; ++k)
     if (per_point[k].status == LIFCAL_START_POINT_OK) std::memcpy(p->pts + 3 * (size_t)k, pts_out.data() + 3 * (size_t)k, 24);
-  if (seconds) *seconds = 1e-3 * (double)ms;
   return 0;
 }
 
@@ -682,21 +590,9 @@ int start_points_impl(const lifcal_intersect_problem* p, const lifcal_ba_options
 
 extern "C" int lifcal_start_poses(const lifcal_resect_problem* p, const lifcal_ba_options* o, double gate_px, double inlier_threshold,
                                   lifcal_start_frame* per_frame, lifcal_start_group* groups, uint32_t* n_groups, double* seconds) {
-  try {   // (no exception crosses the C ABI)
-    return start_poses_impl(p, o, gate_px, inlier_threshold, per_frame, groups, n_groups, seconds);
-  } catch (const std::bad_alloc&) {
-    g_last_error = "lifcal_start_poses: out of host memory"; return LIFCAL_BA_ERR_NOMEM;
-  } catch (...) {
-    g_last_error = "lifcal_start_poses: unexpected exception"; return LIFCAL_BA_ERR_INVALID_ARG;
-  }
+  return guard_abi("lifcal_start_poses", [&] { return start_poses_impl(p, o, gate_px, inlier_threshold, per_frame, groups, n_groups, seconds); });
 }
 
 extern "C" int lifcal_start_points(const lifcal_intersect_problem* p, const lifcal_ba_options* o, double inlier_threshold, lifcal_start_point* per_point, double* seconds) {
-  try {   // (no exception crosses the C ABI)
-    return start_points_impl(p, o, inlier_threshold, per_point, seconds);
-  } catch (const std::bad_alloc&) {
-    g_last_error = "lifcal_start_points: out of host memory"; return LIFCAL_BA_ERR_NOMEM;
-  } catch (...) {
-    g_last_error = "lifcal_start_points: unexpected exception"; return LIFCAL_BA_ERR_INVALID_ARG;
-  }
+  return guard_abi("lifcal_start_points", [&] { return start_points_impl(p, o, inlier_threshold, per_point, seconds); });
 }
