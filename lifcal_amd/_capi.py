@@ -465,6 +465,43 @@ ALIGN_PROTOTYPES = {
     "lifcal_align_apply": (C.c_int, [C.POINTER(Alignment), C.c_uint32, dptr, C.c_uint64, dptr]),
 }
 
+
+class GridImage(C.Structure):           # include/lifcal_grid.h lifcal_grid_image
+    _fields_ = [("data", C.c_void_p), ("bits", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("pitch", C.c_int64)]
+
+
+class GridCentre(C.Structure):          # lifcal_grid_centre: one 48-byte row per lens
+    _fields_ = [("cx", C.c_double), ("cy", C.c_double), ("sum_w", C.c_int64), ("sum_wx", C.c_int64), ("sum_wy", C.c_int64), ("peak", C.c_int64)]
+
+
+GRID_CENTRE_DTYPE = np.dtype([("cx", "<f8"), ("cy", "<f8"), ("sum_w", "<i8"), ("sum_wx", "<i8"), ("sum_wy", "<i8"), ("peak", "<i8")])
+
+
+class GridCentres(C.Structure):         # lifcal_grid_centres
+    _fields_ = [("capacity", C.c_uint64), ("n", C.c_uint64), ("c", C.c_void_p)]
+
+
+class GridLens(C.Structure):            # lifcal_grid_lens: one 32-byte row per centre
+    _fields_ = [("sub", C.c_int32), ("x", C.c_int32), ("y", C.c_int32), ("accepted", C.c_int32), ("dx", C.c_double), ("dy", C.c_double)]
+
+
+GRID_LENS_DTYPE = np.dtype([("sub", "<i4"), ("x", "<i4"), ("y", "<i4"), ("accepted", "<i4"), ("dx", "<f8"), ("dy", "<f8")])
+
+
+class GridReport(C.Structure):          # lifcal_grid_report
+    _fields_ = [("capacity", C.c_uint64), ("lens", C.c_void_p), ("n_centres", C.c_uint64), ("n_accepted", C.c_uint64),
+                ("n_rejected_label", C.c_uint64), ("n_rejected_residual", C.c_uint64), ("rms", C.c_double), ("max_residual", C.c_double),
+                ("lattice_a", C.c_double * 2), ("lattice_b", C.c_double * 2), ("lattice_c", C.c_double * 2),
+                ("lens_diameter", C.c_double), ("rotation", C.c_double), ("lens_base_y", C.c_double * 2), ("origin", C.c_double * 2)]
+
+
+# every symbol include/lifcal_grid.h declares
+GRID_PROTOTYPES = {
+    "lifcal_grid_detect": (C.c_int, [C.POINTER(GridImage), C.c_double, C.c_int32, C.POINTER(GridCentres)]),
+    "lifcal_grid_fit_centres": (C.c_int, [C.c_uint64, dptr, dptr, C.c_int32, C.c_int32, C.c_double, C.c_double, C.POINTER(MlaParams), C.POINTER(GridReport)]),
+    "lifcal_grid_fit": (C.c_int, [C.POINTER(GridImage), C.c_double, C.c_double, C.c_int32, C.POINTER(MlaParams), C.POINTER(GridCentres), C.POINTER(GridReport)]),
+}
+
 # every symbol include/lifcal_prior.h declares
 PRIOR_PROTOTYPES = {
     "lifcal_ba_check_point_priors": (C.c_int, [C.c_uint32, C.POINTER(PointPriors)]),
@@ -577,7 +614,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

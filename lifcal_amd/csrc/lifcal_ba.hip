@@ -102,6 +102,9 @@ constexpr int kNcclFloat64 = 8, kNcclSum = 0;
 
 }  // namespace
 
+// the error text of a translation unit outside this one (grid_fit.hip): the same thread's string, read by lifcal_ba_last_error()
+namespace lifcal { void set_last_error(const char* text) { g_last_error = text; } }
+
 struct lifcal_ba_handle {
   Plan plan;
   lifcal_ba_options opt;

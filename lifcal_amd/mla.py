@@ -49,6 +49,16 @@ class MicroLensGrid:
         self.n_lenses, self.n_web_groups, self.n_web_lines = a.value, b.value, c.value
         self.width, self.height = int(width), int(height)
 
+    @classmethod
+    def from_white_image(cls, white, lens_diameter_guess: float, gate_px: Optional[float] = None, device: int = 0) -> "MicroLensGrid":
+        """The grid measured from a white image (lifcal_grid_fit) instead of read from an MLA calibration
+        file; `grid_fit` on the result holds the fit with its report."""
+        from . import grid_fit
+        fit = grid_fit.fitGrid(white, lens_diameter_guess, grid_fit.DEFAULT_GATE_PX if gate_px is None else gate_px, device)
+        g = fit.grid(device)
+        g.grid_fit = fit
+        return g
+
     def close(self):
         if getattr(self, "_h", None):
             self._lib.lifcal_mla_destroy(self._h)
