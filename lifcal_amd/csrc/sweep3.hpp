@@ -11,7 +11,9 @@
 // the threads.  The hand-off is synchronised PER WAVE PAIR through two LDS counters (steps written / steps read): an evaluator
 // only waits for its accumulator to have read the previous step, an accumulator for its evaluator's next step — no workgroup
 // barrier inside the observation loop, the pair runs one step apart.
-// Everything else — passes, LDS layout, emission targets, factor, Z, Schur product, flush — is k_sweep2's (sweep2.hpp).
+// Everything else — passes, LDS layout, emission targets, factor, Schur product, flush — is k_sweep2's (sweep2.hpp), except Z = L^-1 W:
+// the evaluator lanes add the pose columns already multiplied by L^-1 (emission in two rounds around the factor phase), the Z phase
+// keeps the camera columns.
 // The two roles are two separate code paths on purpose: register allocation is static, a shared path would make every wave
 // carry both roles' accumulators.  Both paths execute the same sequence of workgroup barriers.
 #pragma once
@@ -90,25 +92,32 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
   // ---- phases both roles run with all 512 threads ----
   auto zero_slab = [&]() { for (uint32_t i = tid; i < lay.np_max * SLAB_STRIDE; i += NT) slab[i] = 0.0; };
   auto zero_zd = [&](uint32_t krows) { double2* z2 = reinterpret_cast<double2*>(Zd); for (uint32_t i = tid; i < (krows * zs) / 2; i += NT) z2[i] = double2{0.0, 0.0}; };
-  // Z = L^-1 W in place (pose + camera columns), camera part of W to HBM first; thread = (column, point phase)
+  // Z = L^-1 W in place for the CAMERA columns, the untransformed sum to HBM first (k_backsub reads it from ptacc); thread =
+  // (camera column, point): at most 9 x 64 items.  The pose columns reach barrier P4 final: the evaluator lanes add L^-1 W there
+  // themselves (round B of their emission).
+  // options.deterministic keeps the arithmetic it had, and with it its bits: there the lanes add W itself (they multiply by the
+  // identity instead of L^-1) and this phase transforms the SUM of every column: the pose columns first, thread = (pose column, point).
+  // (The sum of transformed parts differs from the transformed sum in the last bits, and a solve driven to tolerances of 1e-13 turns
+  // last bits into where it stops along the flat (bL0, B) valley: tests/test_gpu_precision1.py.)
   auto z_phase = [&](uint32_t np) {
-    const uint32_t nwc = ncol - 1;
-    const uint32_t nth = NT / nwc > 0 ? NT / nwc : 1;
-    const uint32_t gi = tid / nwc, cidx = tid - gi * nwc;
-    if (gi < nth || nwc > NT) {
-      for (uint32_t cc0 = cidx; cc0 < nwc; cc0 += (nwc > NT ? NT : nwc * nth)) {
-#pragma unroll 4
-        for (uint32_t lp = (nwc > NT ? 0 : gi); lp < np; lp += (nwc > NT ? 1 : nth)) {
-          const double* acc = slab + lp * SLAB_STRIDE;
-          double* z = Zd + (size_t)(3 * lp) * zs + cc0;
-          const double w0 = z[0], w1 = z[zs], w2 = z[2 * zs];
-          if (cc0 >= 6 * nf) {
-            double* ga = d.ptacc + (size_t)pidl[lp] * 36 + 9 + (cc0 - 6 * nf);
-            store_stream(ga, w0); store_stream(ga + NCMAX, w1); store_stream(ga + 2 * NCMAX, w2);
-          }
-          z[0] = acc[0] * w0; z[zs] = acc[1] * w0 + acc[3] * w1; z[2 * zs] = acc[2] * w0 + acc[4] * w1 + acc[5] * w2;
-        }
+    if (d.deterministic != 0) {
+      const uint32_t npc = 6 * nf;
+      for (uint32_t i = tid; i < npc * np; i += NT) {
+        const uint32_t lp = i / npc, cc0 = i - lp * npc;
+        const double* acc = slab + lp * SLAB_STRIDE;
+        double* z = Zd + (size_t)(3 * lp) * zs + cc0;
+        const double w0 = z[0], w1 = z[zs], w2 = z[2 * zs];
+        z[0] = acc[0] * w0; z[zs] = acc[1] * w0 + acc[3] * w1; z[2 * zs] = acc[2] * w0 + acc[4] * w1 + acc[5] * w2;
       }
+    }
+    for (uint32_t i = tid; i < (uint32_t)NC * np; i += NT) {
+      const uint32_t lp = i / (uint32_t)NC, jc = i - lp * (uint32_t)NC;
+      const double* acc = slab + lp * SLAB_STRIDE;
+      double* z = Zd + (size_t)(3 * lp) * zs + 6 * nf + jc;
+      const double w0 = z[0], w1 = z[zs], w2 = z[2 * zs];
+      double* ga = d.ptacc + (size_t)pidl[lp] * 36 + 9 + jc;
+      store_stream(ga, w0); store_stream(ga + NCMAX, w1); store_stream(ga + 2 * NCMAX, w2);
+      z[0] = acc[0] * w0; z[zs] = acc[1] * w0 + acc[3] * w1; z[2 * zs] = acc[2] * w0 + acc[4] * w1 + acc[5] * w2;
     }
   };
   // rotation, rotated point and d(R P)/d(angles) of a lane's (point, frame)
@@ -164,7 +173,8 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
   // unit serialises lanes that hit one address in lane order
   const bool det = d.deterministic != 0;
   uint32_t* turn = (uint32_t*)(misc + 8) + (role_b ? 1 : 0);
-  uint32_t my_turn = wl;                                    // + WR per pass
+  // Evaluators take TWO turns per wave and pass: round A of waves 0..WR-1, then (wave 0 factors) round B of waves 0..WR-1.
+  uint32_t my_turn = wl;                                    // accumulators: + WR per pass; evaluators: + 2 WR (round B is turn my_turn + WR)
   // acquire / release at workgroup scope: the consumer's reads of the hand-off buffer may not be hoisted above the wait, the
   // producer's writes may not sink below the publish (on gfx950 both order LDS through lgkmcnt; no cache maintenance is involved)
   auto wait_for = [](uint32_t* flag, uint32_t need) {
@@ -173,6 +183,56 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
   auto publish = [](uint32_t* flag, uint32_t value) {
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's LDS traffic of this step is done before the counter moves
     __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+  };
+  uint32_t* factor_done = (uint32_t*)(misc + 3) + 1;       // passes whose points evaluator wave 0 has factored (monotone; argued where it is published)
+  // ---- one thread per point: damp, factor U = L L^T (k_sweep2 phase 2); run by evaluator wave 0 (np <= 64) ----
+  auto factor_points = [&](uint32_t np, uint32_t p, double fsg0, double fsg1, double fsg2) {
+    if (tid < np) {
+      pidl[tid] = p;
+      double* acc = slab + tid * SLAB_STRIDE;
+      double U0 = acc[0], U1 = acc[1], U2 = acc[2], U3 = acc[3], U4 = acc[4], U5 = acc[5];
+      if (mode == 1) {
+        double* ga = d.ptacc + (size_t)p * 36;
+        store_stream(ga, U0); store_stream(ga + 3, U3); store_stream(ga + 5, U5);
+      } else {
+        const double g0 = acc[6], g1 = acc[7], g2 = acc[8];
+        double lam[3];
+        {
+          const double h[3] = {U0, U3, U5}, sgv[3] = {fsg0, fsg1, fsg2};
+#pragma unroll
+          for (int k = 0; k < 3; ++k) { const double sg = sgv[k]; lam[k] = fmin(fmax(h[k] * sg * sg, d.lm_min), d.lm_max) / (lm_radius(d, radius) * sg * sg); }
+        }
+        U0 += lam[0]; U3 += lam[1]; U5 += lam[2];
+        bool ok = U0 > 0.0;
+        double i00 = rsqrt(U0);
+        const double l10 = U1 * i00, l20 = U2 * i00;
+        const double d11 = U3 - l10 * l10; ok = ok && (d11 > 0.0);
+        double i11 = rsqrt(d11);
+        const double l21 = (U4 - l20 * l10) * i11;
+        const double d22 = U5 - l20 * l20 - l21 * l21; ok = ok && (d22 > 0.0);
+        double i22 = rsqrt(d22);
+        double m10 = -l10 * i00 * i11, m21 = -l21 * i11 * i22, m20 = -(l20 * i00 + l21 * m10) * i22;
+        if (!ok) { i00 = i11 = i22 = m10 = m21 = m20 = 0.0; atomicAdd(misc + 1, 1.0); }   // (the lanes of the point then add zeros to Z)
+        double* gu = d.Uinv + 9 * (size_t)p;
+        const double v00 = i00 * i00 + m10 * m10 + m20 * m20, v01 = m10 * i11 + m20 * m21, v02 = m20 * i22;
+        const double v11 = i11 * i11 + m21 * m21, v12 = m21 * i22, v22 = i22 * i22;
+        {
+          const double vu[9] = {v00, v01, v02, v01, v11, v12, v02, v12, v22};
+#pragma unroll
+          for (int k = 0; k < 9; ++k) store_stream(gu + k, vu[k]);
+        }
+        double* gl = d.lamP + 3 * (size_t)p;
+        double* ga = d.ptacc + (size_t)p * 36 + 6;
+#pragma unroll
+        for (int k = 0; k < 3; ++k) store_stream(gl + k, lam[k]);
+        store_stream(ga, g0); store_stream(ga + 1, g1); store_stream(ga + 2, g2);
+        const double gm = fmax(fabs(g0), fmax(fabs(g1), fabs(g2)));
+        atomicMax((unsigned long long*)(misc + 2), (unsigned long long)__double_as_longlong(gm));
+        acc[0] = i00; acc[1] = m10; acc[2] = m20; acc[3] = i11; acc[4] = m21; acc[5] = i22;
+        double* z0 = Zd + (size_t)(3 * tid) * zs + (ncol - 1);
+        z0[0] = i00 * g0; z0[zs] = m10 * g0 + i11 * g1; z0[2 * zs] = m20 * g0 + m21 * g1 + i22 * g2;
+      }
+    }
   };
 
   // Schur product: 4x4 micro-tiles over the lower triangle, software-pipelined.  With one tile per thread (ntri <= 256) the
@@ -404,21 +464,78 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
       if (mode == 0) zero_zd(krows);
       lds_barrier();                                                                                    // ---- barrier P2
       asm volatile("" :: "v"(fsg0), "v"(fsg1), "v"(fsg2));
+      // The emission runs in two rounds around the factor phase.  Round A: U and g of the lane's point, all the factor phase
+      // reads.  Round B: the frame-level values, then, once the point is factored, the lane's share of Z = L^-1 W for its six pose
+      // columns: the lane applies L^-1 to W while it still holds it, and the Z phase keeps the camera columns only.  L^-1 is
+      // linear, so the transformed parts of the lanes of a group (and of the groups of a split point) add up to the transformed sum.
+      const double Am[3][3] = {{A[0], A[1], A[2]}, {A[1], A[3], A[4]}, {A[2], A[4], A[5]}};
+      const double (&R)[9] = q.R; const double (&Gr)[3][3] = q.Gr;
+      double* acc = slab + lp * SLAB_STRIDE;
+      // ---- round A ----
       if (det) wait_for(turn, my_turn);
       if (cnt > 0) {
-        const double Am[3][3] = {{A[0], A[1], A[2]}, {A[1], A[3], A[4]}, {A[2], A[4], A[5]}};
-        const double (&R)[9] = q.R; const double (&Gr)[3][3] = q.Gr;
-        double AG[3][3], GAG[3][3];
+        double AR[3][3];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
-          for (int j = 0; j < 3; ++j) AG[i][j] = Am[i][0] * Gr[0][j] + Am[i][1] * Gr[1][j] + Am[i][2] * Gr[2][j];
+          for (int j = 0; j < 3; ++j) AR[i][j] = Am[i][0] * R[j] + Am[i][1] * R[3 + j] + Am[i][2] * R[6 + j];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+#pragma unroll
+          for (int j = 0; j <= i; ++j) {
+            const double u_ij = R[i] * AR[0][j] + R[3 + i] * AR[1][j] + R[6 + i] * AR[2][j];
+            const int pos = (i == 0) ? 0 : (i == 1 ? (j == 0 ? 1 : 3) : (j == 0 ? 2 : (j == 1 ? 4 : 5)));
+            atomicAdd(acc + pos, u_ij);
+          }
+        }
+        if (mode == 0) {
+          { double* ga = d.Av + (size_t)gidx * 6;   // 48 bytes per lane, 16-byte aligned: three 16-byte stores
+            store_stream(ga, A[0], A[1]); store_stream(ga + 2, A[2], A[3]); store_stream(ga + 4, A[4], A[5]); }
+#pragma unroll
+          for (int i = 0; i < 3; ++i) atomicAdd(acc + 6 + i, R[i] * bv[0] + R[3 + i] * bv[1] + R[6 + i] * bv[2]);
+        }
+      }
+      if (det) publish(turn, my_turn + 1);
+      STAMP(6);
+      // The factor phase reads only what round A emitted (U, g of the points) and runs on wave 0 (np <= 64): it waits for the
+      // evaluator waves through an LDS counter instead of a workgroup barrier, so it runs under round B of the other evaluator
+      // waves and under the longer emission of the accumulator waves; everybody meets again at barrier P4.
+      // (options.deterministic: eval_done is bumped behind the wave's turn of round A, so the same wait serves.)
+      // Wave 0 factors BETWEEN its rounds.  With its frame-level values in front of the factor (every wave in one order: A, frame
+      // values, factor on wave 0, Z) the wait for eval_done shrinks from 10.9 k to 2.3 k cycles per block, the emission grows by as
+      // much and the step measures the same (profiles/sweep_zfused/).
+      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+      if (lane == 0) __hip_atomic_fetch_add(eval_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+      ++passes_done;
+      if (w == 0) {
+        wait_for(eval_done, (uint32_t)WR * passes_done);
+        STAMP(1);
+        factor_points(np, fp, fsg0, fsg1, fsg2);
+        // factor_done: passes whose points are factored.  Monotone, zeroed with misc.  Wave 0 is resident as long as any wave of
+        // the workgroup is (the early return on LM_TERMINATION is taken by the whole grid in front of everything), it gets here
+        // in every pass on every path — the factor's body is under `tid < np` and the lanes' round A under `cnt > 0`, the
+        // counters are not — and its only wait on the way is eval_done, which every evaluator wave bumps right behind its own
+        // round A without waiting for anybody (deterministic mode: behind its turn of round A, turns that wave 0 opens itself
+        // and that are handed on unconditionally).  No wave waits for factor_done in front of its eval_done bump, so the two
+        // counters cannot wait for each other; np of 1 or 64, idle lanes and fixed frames change lane masks only.
+        publish(factor_done, passes_done);   // (behind s_waitcnt lgkmcnt(0): L^-1 in the slab and the rhs column of Z are written)
+        STAMP(2);
+      }
+      // ---- round B ----
+      if (det) wait_for(turn, my_turn + (uint32_t)WR);
+      const bool fpose = cnt > 0 && d.frame_live[fr] != 0;   // 0: the pose of this frame is held constant (lifcal_ba_set_fixed_frames): no pose columns
+      double AG[3][3];
+#pragma unroll
+      for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) AG[i][j] = Am[i][0] * Gr[0][j] + Am[i][1] * Gr[1][j] + Am[i][2] * Gr[2][j];
+      if (cnt > 0) {
+        double GAG[3][3];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
           for (int j = 0; j < 3; ++j) GAG[i][j] = Gr[0][i] * AG[0][j] + Gr[1][i] * AG[1][j] + Gr[2][i] * AG[2][j];
         RunMask rm = run_masks(cnt, lf);
-        const bool fpose = d.frame_live[fr] != 0;   // 0: the pose of this frame is held constant (lifcal_ba_set_fixed_frames): no pose columns
         rm.head = rm.head && fpose;
         double* fr_acc = Fr + lf;
         {
@@ -438,104 +555,44 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
 #pragma unroll
           for (int a = 0; a < 3; ++a) { const double v = run_sum(bv[a], rm); if (rm.head) atomicAdd(fr_acc + (size_t)(24 + a) * frs, v); }
         }
-        double AR[3][3];
+      }
+      if (mode == 0) {
+        // the points of this pass are factored: the slab holds L^-1 (zeros where U was not positive definite).
+        // options.deterministic: the lanes add W itself, times the identity (exact), and the Z phase transforms the sums as it always
+        // did (see z_phase), so the mode's results keep their bits; the wait is not needed then.
+        if (!det) wait_for(factor_done, passes_done);
+        if (fpose) {
+          double i00 = 1.0, m10 = 0.0, m20 = 0.0, i11 = 1.0, m21 = 0.0, i22 = 1.0;
+          if (!det) { i00 = acc[0]; m10 = acc[1]; m20 = acc[2]; i11 = acc[3]; m21 = acc[4]; i22 = acc[5]; }
+          // The row stride of Z is even (16-byte rows for the Schur product's double2 reads) and so is the frame stride 6: with
+          // the same column j in every lane an f64 atomic instruction reaches only the EVEN double-banks (4-way conflicts over
+          // 64 lanes).  Lanes of odd points therefore take the six columns rotated by one: step jj adds column jj + 1.
+          // W = R^T [A Gr | A] is built one column at a time (three values live instead of eighteen).
+          double* zcol = Zd + (size_t)(3 * lp) * zs + 6 * lf;
+          const bool rot = (lp & 1u) != 0;
 #pragma unroll
-        for (int i = 0; i < 3; ++i)
+          for (int jj = 0; jj < 6; ++jj) {
+            const int ja = jj, jb = (jj + 1) % 6;
+            double x[3];
 #pragma unroll
-          for (int j = 0; j < 3; ++j) AR[i][j] = Am[i][0] * R[j] + Am[i][1] * R[3 + j] + Am[i][2] * R[6 + j];
-        double* acc = slab + lp * SLAB_STRIDE;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-#pragma unroll
-          for (int j = 0; j <= i; ++j) {
-            const double u_ij = R[i] * AR[0][j] + R[3 + i] * AR[1][j] + R[6 + i] * AR[2][j];
-            const int pos = (i == 0) ? 0 : (i == 1 ? (j == 0 ? 1 : 3) : (j == 0 ? 2 : (j == 1 ? 4 : 5)));
-            atomicAdd(acc + pos, u_ij);
-          }
-        }
-        if (mode == 0) {
-          { double* ga = d.Av + (size_t)gidx * 6;   // 48 bytes per lane, 16-byte aligned: three 16-byte stores
-            store_stream(ga, A[0], A[1]); store_stream(ga + 2, A[2], A[3]); store_stream(ga + 4, A[4], A[5]); }
-#pragma unroll
-          for (int i = 0; i < 3; ++i) {
-            atomicAdd(acc + 6 + i, R[i] * bv[0] + R[3 + i] * bv[1] + R[6 + i] * bv[2]);
-            // The row stride of Z is even (16-byte rows for the Schur product's double2 reads) and so is the frame stride 6: with
-            // the same column j in every lane an f64 atomic instruction reaches only the EVEN double-banks (4-way conflicts over
-            // 64 lanes).  Lanes of odd points therefore take the six columns rotated by one: instruction jj adds column jj + 1.
-            double* zrow = Zd + (size_t)(3 * lp + i) * zs + 6 * lf;
-            double w6[6];
-#pragma unroll
-            for (int j = 0; j < 3; ++j) { w6[j] = R[i] * AG[0][j] + R[3 + i] * AG[1][j] + R[6 + i] * AG[2][j]; w6[3 + j] = R[i] * Am[0][j] + R[3 + i] * Am[1][j] + R[6 + i] * Am[2][j]; }
-            const bool rot = (lp & 1u) != 0;
-#pragma unroll
-            for (int jj = 0; jj < 6; ++jj) {
-              const double wv = rot ? w6[(jj + 1) % 6] : w6[jj];
-              const uint32_t col = rot ? (uint32_t)((jj + 1) % 6) : (uint32_t)jj;
-              if (fpose) atomicAdd(zrow + col, wv);
+            for (int k = 0; k < 3; ++k) {
+              const double xa = ja < 3 ? AG[k][ja % 3] : Am[k][ja % 3], xb = jb < 3 ? AG[k][jb % 3] : Am[k][jb % 3];
+              x[k] = rot ? xb : xa;
             }
+            const uint32_t col = rot ? (uint32_t)jb : (uint32_t)ja;
+            const double w0 = R[0] * x[0] + R[3] * x[1] + R[6] * x[2];
+            const double w1 = R[1] * x[0] + R[4] * x[1] + R[7] * x[2];
+            const double w2 = R[2] * x[0] + R[5] * x[1] + R[8] * x[2];
+            atomicAdd(zcol + col, i00 * w0);
+            atomicAdd(zcol + zs + col, m10 * w0 + i11 * w1);
+            atomicAdd(zcol + 2 * zs + col, m20 * w0 + m21 * w1 + i22 * w2);
           }
         }
       }
-      if (det) { publish(turn, my_turn + 1); my_turn += (uint32_t)WR; }
+      if (det) { publish(turn, my_turn + (uint32_t)WR + 1); my_turn += 2u * (uint32_t)WR; }
       STAMP(6);
-      // The factor phase reads only what the EVALUATOR waves emitted (U, g of the points) and runs on wave 0 (np <= 64): it
-      // waits for the four evaluator waves through an LDS counter instead of a workgroup barrier, so it overlaps the longer
-      // emission of the accumulator waves (81 vs 54 LDS atomics per lane); everybody meets again at barrier P4.
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      if (lane == 0) __hip_atomic_fetch_add(eval_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-      ++passes_done;
-      if (w == 0) wait_for(eval_done, (uint32_t)WR * passes_done);
-      STAMP(1);
-      // ---- one thread per point: damp, factor U = L L^T (k_sweep2 phase 2) ----
-      if (tid < np) {
-        const uint32_t p = fp;
-        pidl[tid] = p;
-        double* acc = slab + tid * SLAB_STRIDE;
-        double U0 = acc[0], U1 = acc[1], U2 = acc[2], U3 = acc[3], U4 = acc[4], U5 = acc[5];
-        if (mode == 1) {
-          double* ga = d.ptacc + (size_t)p * 36;
-          store_stream(ga, U0); store_stream(ga + 3, U3); store_stream(ga + 5, U5);
-        } else {
-          const double g0 = acc[6], g1 = acc[7], g2 = acc[8];
-          double lam[3];
-          {
-            const double h[3] = {U0, U3, U5}, sgv[3] = {fsg0, fsg1, fsg2};
-#pragma unroll
-            for (int k = 0; k < 3; ++k) { const double sg = sgv[k]; lam[k] = fmin(fmax(h[k] * sg * sg, d.lm_min), d.lm_max) / (lm_radius(d, radius) * sg * sg); }
-          }
-          U0 += lam[0]; U3 += lam[1]; U5 += lam[2];
-          bool ok = U0 > 0.0;
-          double i00 = rsqrt(U0);
-          const double l10 = U1 * i00, l20 = U2 * i00;
-          const double d11 = U3 - l10 * l10; ok = ok && (d11 > 0.0);
-          double i11 = rsqrt(d11);
-          const double l21 = (U4 - l20 * l10) * i11;
-          const double d22 = U5 - l20 * l20 - l21 * l21; ok = ok && (d22 > 0.0);
-          double i22 = rsqrt(d22);
-          double m10 = -l10 * i00 * i11, m21 = -l21 * i11 * i22, m20 = -(l20 * i00 + l21 * m10) * i22;
-          if (!ok) { i00 = i11 = i22 = m10 = m21 = m20 = 0.0; atomicAdd(misc + 1, 1.0); }
-          double* gu = d.Uinv + 9 * (size_t)p;
-          const double v00 = i00 * i00 + m10 * m10 + m20 * m20, v01 = m10 * i11 + m20 * m21, v02 = m20 * i22;
-          const double v11 = i11 * i11 + m21 * m21, v12 = m21 * i22, v22 = i22 * i22;
-          {
-            const double vu[9] = {v00, v01, v02, v01, v11, v12, v02, v12, v22};
-#pragma unroll
-            for (int k = 0; k < 9; ++k) store_stream(gu + k, vu[k]);
-          }
-          double* gl = d.lamP + 3 * (size_t)p;
-          double* ga = d.ptacc + (size_t)p * 36 + 6;
-#pragma unroll
-          for (int k = 0; k < 3; ++k) store_stream(gl + k, lam[k]);
-          store_stream(ga, g0); store_stream(ga + 1, g1); store_stream(ga + 2, g2);
-          const double gm = fmax(fabs(g0), fmax(fabs(g1), fabs(g2)));
-          atomicMax((unsigned long long*)(misc + 2), (unsigned long long)__double_as_longlong(gm));
-          acc[0] = i00; acc[1] = m10; acc[2] = m20; acc[3] = i11; acc[4] = m21; acc[5] = i22;
-          double* z0 = Zd + (size_t)(3 * tid) * zs + (ncol - 1);
-          z0[0] = i00 * g0; z0[zs] = m10 * g0 + i11 * g1; z0[2 * zs] = m20 * g0 + m21 * g1 + i22 * g2;
-        }
-      }
       lds_barrier();                                                                                    // ---- barrier P4
-      STAMP(2);
+      STAMP(15);
       if (mode == 0) {
         z_phase(np);
         lds_barrier();                                                                                  // ---- barrier P5

@@ -18,7 +18,7 @@ lib.lifcal_ba_debug_stamps.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32]
 n = lib.lifcal_ba_debug_stamps(ba._h, buf.ctypes.data, info.n_chunks)
 st = buf.reshape(-1, 32)[:n].astype(np.float64)
 names = ["zero+sync", "phase1 wait@sync", "phase2 factor", "phase3 W->HBM,Z", "phase4 schur", "flush to HBM", "phase1 emission(w0)", "phase1 obs loop(w0)",
-         "(slack)", "tile emit", "cc/gc/cost reduce", "replica fold", "pass top (prefetch issue)", "zero stores", "prologue", "",
+         "(slack)", "tile emit", "cc/gc/cost reduce", "replica fold", "pass top (prefetch issue)", "zero stores", "prologue", "wait at P4 (k_sweep3)",
          "acc: pass top", "acc: obs loop", "acc: P2a+zero+P2", "acc: emission", "acc: wait P4", "acc: Z + Schur half", "", "", "", "", "", "", "", "", "", ""]
 tot = st[:, :16].sum(1)
 print(f"{name}: blocks {n}, sweep {r.seconds*1e6:.1f} us; cycles per block: mean {tot.mean():.0f} max {tot.max():.0f} min {tot.min():.0f}")
