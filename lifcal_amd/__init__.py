@@ -14,3 +14,4 @@ from .intersection import intersectPoints, IntersectionResult  # noqa: F401
 from .start import startPoses, startPoints, StartPosesResult, StartPointsResult  # noqa: F401
 from .register import registerScene, RegisterResult  # noqa: F401
 from .grid_fit import detectLensCentres, fitGridCentres, fitGrid, GridFit, GridReport  # noqa: F401
+from .raw_depth import estimateRawDepth, checkRawDepth, RawDepth, RawPoints  # noqa: F401

@@ -502,6 +502,36 @@ GRID_PROTOTYPES = {
     "lifcal_grid_fit": (C.c_int, [C.POINTER(GridImage), C.c_double, C.c_double, C.c_int32, C.POINTER(MlaParams), C.POINTER(GridCentres), C.POINTER(GridReport)]),
 }
 
+class RawDepthImage(C.Structure):       # include/lifcal_rawdepth.h lifcal_rawdepth_image
+    _fields_ = [("data", C.c_void_p), ("bits", C.c_int32), ("width", C.c_int32), ("height", C.c_int32), ("on_device", C.c_int32), ("pitch", C.c_int64)]
+
+
+class RawDepthOptions(C.Structure):     # lifcal_rawdepth_options
+    _fields_ = [("n_hyp", C.c_int32), ("patch_radius", C.c_int32), ("min_neighbours", C.c_int32), ("min_contrast", C.c_int32),
+                ("iv_min", C.c_double), ("iv_max", C.c_double), ("max_baseline", C.c_double), ("ambiguity_ratio", C.c_double)]
+
+
+class RawDepthPlan(C.Structure):        # lifcal_rawdepth_plan
+    _fields_ = [("options", RawDepthOptions), ("n_neighbours", C.c_int32), ("window", C.c_int32), ("lds_bytes", C.c_int32), ("reserved", C.c_int32)]
+
+
+class RawDepthResult(C.Structure):      # lifcal_rawdepth_result
+    _fields_ = [("out_on_device", C.c_int32), ("n_neighbours_used", C.c_int32), ("inv_depth", C.c_void_p), ("cost", C.c_void_p),
+                ("status", C.c_void_p), ("n_neighbours", C.c_void_p), ("count", C.c_uint64 * 5), ("seconds", C.c_double)]
+
+
+class RawDepthPointList(C.Structure):   # lifcal_rawdepth_point_list
+    _fields_ = [("inv_depth", C.c_void_p), ("on_device", C.c_int32), ("depth_to_raw_im_scale", C.c_int32), ("capacity", C.c_uint64), ("n", C.c_uint64),
+                ("x", dptr), ("y", dptr), ("vdepth", dptr), ("src", uptr), ("lens", _iptr)]
+
+
+# every symbol include/lifcal_rawdepth.h declares
+RAWDEPTH_PROTOTYPES = {
+    "lifcal_rawdepth_check": (C.c_int, [C.POINTER(MlaParams), C.POINTER(RawDepthImage), C.POINTER(RawDepthOptions), C.POINTER(RawDepthPlan)]),
+    "lifcal_rawdepth_estimate": (C.c_int, [C.c_void_p, C.POINTER(RawDepthImage), C.POINTER(RawDepthOptions), C.POINTER(RawDepthResult)]),
+    "lifcal_rawdepth_points": (C.c_int, [C.c_void_p, C.POINTER(RawDepthPointList)]),
+}
+
 # every symbol include/lifcal_prior.h declares
 PRIOR_PROTOTYPES = {
     "lifcal_ba_check_point_priors": (C.c_int, [C.c_uint32, C.POINTER(PointPriors)]),
@@ -614,7 +644,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

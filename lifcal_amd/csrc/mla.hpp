@@ -10,6 +10,7 @@
 #include <hipcub/hipcub.hpp>
 
 #include "../../include/lifcal_mla.h"
+#include "raw_depth.hpp"
 
 namespace mla {
 
@@ -39,6 +40,7 @@ struct Host {
   std::vector<Line> web;            // flattened epiLineWeb
   std::vector<int32_t> web_group;
   int32_t n_groups = 0;
+  int32_t n_sub0 = 0;               // lenses of sub-grid 0: they come first in the list
 };
 
 // MicroLensGrid::readInGrid, the values derived from the file (src/MicroLensGrid/MicroLensGrid.cpp:60-63, 107-111, 165-166)
@@ -86,6 +88,7 @@ inline void build_lenses(Host& g) {
         g.cx.push_back(lx); g.cy.push_back(ly); g.type.push_back(t);
       }
     }
+    if (k == 0) g.n_sub0 = (int32_t)g.cx.size();
   }
 }
 
@@ -333,6 +336,13 @@ inline int select_device(int32_t device, const char* who) {
 }
 
 }  // namespace mla
+
+// raw_depth.hpp: the handle's device arrays for raw_depth.hip, which lives in a code object of its own
+bool lifcal::mla_view(const lifcal_mla_handle* h, lifcal::MlaView* out) {
+  if (!h || !out) return false;
+  *out = lifcal::MlaView{h->host.prm, h->device, h->dev.n_lenses, h->host.n_sub0, h->host.valid_r, h->dev.cx, h->dev.cy, h->dev.map_ml};
+  return true;
+}
 
 extern "C" {
 

@@ -48,6 +48,13 @@ class MicroLensGrid:
         _check(self._lib.lifcal_mla_info(self._h, C.byref(a), C.byref(b), C.byref(c)), "lifcal_mla_info")
         self.n_lenses, self.n_web_groups, self.n_web_lines = a.value, b.value, c.value
         self.width, self.height = int(width), int(height)
+        self.device = int(device)
+
+    def estimateRawDepth(self, raw, **options):
+        """Virtual depth per raw pixel from a plane sweep between the micro images (lifcal_rawdepth_estimate, DESIGN.md
+        section 7t): raw_depth.estimateRawDepth on this grid."""
+        from . import raw_depth
+        return raw_depth.estimateRawDepth(self, raw, **options)
 
     @classmethod
     def from_white_image(cls, white, lens_diameter_guess: float, gate_px: Optional[float] = None, device: int = 0) -> "MicroLensGrid":
