@@ -532,6 +532,27 @@ RAWDEPTH_PROTOTYPES = {
     "lifcal_rawdepth_points": (C.c_int, [C.c_void_p, C.POINTER(RawDepthPointList)]),
 }
 
+class DepthMapOptions(C.Structure):     # include/lifcal_depthmap.h lifcal_depthmap_options
+    _fields_ = [("scale", C.c_int32), ("out_width", C.c_int32), ("out_height", C.c_int32), ("min_support", C.c_int32), ("fill_rounds", C.c_int32),
+                ("fill_min_neighbours", C.c_int32), ("tol_iv", C.c_double), ("iv_min", C.c_double)]
+
+
+class DepthMapPlan(C.Structure):        # lifcal_depthmap_plan
+    _fields_ = [("options", DepthMapOptions), ("out_width", C.c_int32), ("out_height", C.c_int32), ("tq", C.c_int32), ("max_side", C.c_int32),
+                ("max_samples_per_cell", C.c_int64)]
+
+
+class DepthMapResult(C.Structure):      # lifcal_depthmap_result
+    _fields_ = [("out_on_device", C.c_int32), ("reserved", C.c_int32), ("inv_depth", C.c_void_p), ("depth16", C.c_void_p), ("status", C.c_void_p),
+                ("support", C.c_void_p), ("count", C.c_uint64 * 4), ("n_samples", C.c_uint64), ("seconds", C.c_double)]
+
+
+# every symbol include/lifcal_depthmap.h declares
+DEPTHMAP_PROTOTYPES = {
+    "lifcal_depthmap_check": (C.c_int, [C.POINTER(MlaParams), C.c_int32, C.c_int32, C.POINTER(DepthMapOptions), C.POINTER(DepthMapPlan)]),
+    "lifcal_depthmap_from_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DepthMapOptions), C.POINTER(DepthMapResult)]),
+}
+
 # every symbol include/lifcal_prior.h declares
 PRIOR_PROTOTYPES = {
     "lifcal_ba_check_point_priors": (C.c_int, [C.c_uint32, C.POINTER(PointPriors)]),
@@ -644,7 +665,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -109,6 +109,12 @@ class RawDepth:
         pts = self.points(scale)
         return pts, depth.backProjectPoints(pts.x, pts.y, pts.vdepth, cam, config, spx, spy, **kw)
 
+    def depth_map(self, device_out: bool = False, **options):
+        """inv_depth resampled onto the virtual-image grid in the depth PNG's encoding (depth_map.depthMapFromRaw, whose options
+        pass through)."""
+        from . import depth_map
+        return depth_map.depthMapFromRaw(self.grid, self.inv_depth, device_out=device_out, **options)
+
 
 def checkRawDepth(params: capi.MlaParams, raw, **options) -> capi.RawDepthPlan:
     """lifcal_rawdepth_check: the argument checks of estimateRawDepth for a grid with these parameters; needs no device."""
