@@ -16,3 +16,4 @@ from .register import registerScene, RegisterResult  # noqa: F401
 from .grid_fit import detectLensCentres, fitGridCentres, fitGrid, GridFit, GridReport  # noqa: F401
 from .raw_depth import estimateRawDepth, checkRawDepth, RawDepth, RawPoints  # noqa: F401
 from .depth_map import depthMapFromRaw, checkDepthMap, VirtualDepthMap  # noqa: F401
+from .total_focus import totalFocusImage, checkTotalFocus, TotalFocusImage  # noqa: F401

@@ -553,6 +553,29 @@ DEPTHMAP_PROTOTYPES = {
     "lifcal_depthmap_from_raw": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int32, C.POINTER(DepthMapOptions), C.POINTER(DepthMapResult)]),
 }
 
+class TotalFocusOptions(C.Structure):   # include/lifcal_totalfocus.h lifcal_totalfocus_options
+    _fields_ = [("scale", C.c_int32), ("out_width", C.c_int32), ("out_height", C.c_int32), ("min_lenses", C.c_int32), ("white_level", C.c_int32),
+                ("margin", C.c_double), ("max_reach", C.c_double), ("iv_min", C.c_double), ("default_iv", C.c_double)]
+
+
+class TotalFocusPlan(C.Structure):      # lifcal_totalfocus_plan
+    _fields_ = [("options", TotalFocusOptions), ("out_width", C.c_int32), ("out_height", C.c_int32), ("r_use", C.c_double),
+                ("max_lenses_per_cell", C.c_int32), ("reserved", C.c_int32)]
+
+
+class TotalFocusResult(C.Structure):    # lifcal_totalfocus_result
+    _fields_ = [("out_on_device", C.c_int32), ("reserved", C.c_int32), ("image", C.c_void_p), ("n_lenses", C.c_void_p), ("status", C.c_void_p),
+                ("count", C.c_uint64 * 4), ("seconds", C.c_double)]
+
+
+# every symbol include/lifcal_totalfocus.h declares
+TOTALFOCUS_PROTOTYPES = {
+    "lifcal_totalfocus_check": (C.c_int, [C.POINTER(MlaParams), C.POINTER(RawDepthImage), C.POINTER(RawDepthImage), C.c_int32, C.c_int32,
+                                          C.POINTER(TotalFocusOptions), C.POINTER(TotalFocusPlan)]),
+    "lifcal_totalfocus_render": (C.c_int, [C.c_void_p, C.POINTER(RawDepthImage), C.POINTER(RawDepthImage), C.c_void_p, C.c_int32,
+                                           C.POINTER(TotalFocusOptions), C.POINTER(TotalFocusResult)]),
+}
+
 # every symbol include/lifcal_prior.h declares
 PRIOR_PROTOTYPES = {
     "lifcal_ba_check_point_priors": (C.c_int, [C.c_uint32, C.POINTER(PointPriors)]),
@@ -665,7 +688,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()) + list(TOTALFOCUS_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -57,6 +57,14 @@ class VirtualDepthMap:
         depth_maps.setMaps(self.depth16, first=int(index))
         return depth_maps
 
+    def total_focus(self, grid, image, white=None, **options):
+        """The total-focus image of the raw image at this map's depths (total_focus.totalFocusImage with this map's inv_depth and
+        scale, whose other options pass through).  The maps come back on the device when this map is there."""
+        from . import total_focus
+        options.setdefault("device_out", hasattr(self.inv_depth, "data_ptr"))
+        options.update(scale=self.scale, out_width=int(self.inv_depth.shape[1]), out_height=int(self.inv_depth.shape[0]))
+        return total_focus.totalFocusImage(grid, image, self.inv_depth, white=white, **options)
+
 
 def checkDepthMap(params: capi.MlaParams, width: int, height: int, **options) -> capi.DepthMapPlan:
     """lifcal_depthmap_check: the argument checks of depthMapFromRaw for a grid with these parameters; needs no device."""

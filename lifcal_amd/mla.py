@@ -56,6 +56,12 @@ class MicroLensGrid:
         from . import raw_depth
         return raw_depth.estimateRawDepth(self, raw, **options)
 
+    def totalFocusImage(self, image, inv_depth, white=None, **options):
+        """The all-in-focus picture on the virtual-image grid from a raw image and a virtual-image depth map
+        (lifcal_totalfocus_render): total_focus.totalFocusImage on this grid."""
+        from . import total_focus
+        return total_focus.totalFocusImage(self, image, inv_depth, white=white, **options)
+
     @classmethod
     def from_white_image(cls, white, lens_diameter_guess: float, gate_px: Optional[float] = None, device: int = 0) -> "MicroLensGrid":
         """The grid measured from a white image (lifcal_grid_fit) instead of read from an MLA calibration
