@@ -17,3 +17,4 @@ from .grid_fit import detectLensCentres, fitGridCentres, fitGrid, GridFit, GridR
 from .raw_depth import estimateRawDepth, checkRawDepth, RawDepth, RawPoints  # noqa: F401
 from .depth_map import depthMapFromRaw, checkDepthMap, VirtualDepthMap  # noqa: F401
 from .total_focus import totalFocusImage, checkTotalFocus, TotalFocusImage  # noqa: F401
+from .features import detectFeatures, matchFeatures, linkTracks, trackSequence, checkFeatures, Features, Matches, Tracks  # noqa: F401

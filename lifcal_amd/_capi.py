@@ -576,6 +576,47 @@ TOTALFOCUS_PROTOTYPES = {
                                            C.POINTER(TotalFocusOptions), C.POINTER(TotalFocusResult)]),
 }
 
+class FeaturesOptions(C.Structure):     # include/lifcal_features.h lifcal_features_options
+    _fields_ = [("win_r", C.c_int32), ("nms_r", C.c_int32), ("cell", C.c_int32), ("per_cell", C.c_int32), ("min_score", C.c_double)]
+
+
+class FeaturesPlan(C.Structure):        # lifcal_features_plan
+    _fields_ = [("options", FeaturesOptions), ("buckets_x", C.c_int32), ("buckets_y", C.c_int32), ("max_features", C.c_int64)]
+
+
+class FeaturesList(C.Structure):        # lifcal_features_list
+    _fields_ = [("capacity", C.c_uint64), ("n", C.c_uint64), ("x", dptr), ("y", dptr), ("ix", _iptr), ("iy", _iptr), ("score", dptr), ("desc", uptr),
+                ("seconds", C.c_double)]
+
+
+class FeaturesSet(C.Structure):         # lifcal_features_set
+    _fields_ = [("n_frames", C.c_uint32), ("reserved", C.c_uint32), ("offset", uptr), ("desc", uptr), ("ix", _iptr), ("iy", _iptr)]
+
+
+class MatchOptions(C.Structure):        # lifcal_match_options
+    _fields_ = [("max_dist", C.c_int32), ("ratio_num", C.c_int32), ("ratio_den", C.c_int32), ("max_shift", C.c_int32)]
+
+
+class MatchList(C.Structure):           # lifcal_match_list
+    _fields_ = [("capacity", C.c_uint64), ("n", C.c_uint64), ("pair_start", C.POINTER(C.c_uint64)), ("i", uptr), ("j", uptr), ("dist", uptr),
+                ("seconds", C.c_double)]
+
+
+class Tracks(C.Structure):              # lifcal_tracks
+    _fields_ = [("min_length", C.c_uint32), ("n_tracks", C.c_uint32), ("n_conflicts", C.c_uint64), ("capacity", C.c_uint64), ("n", C.c_uint64),
+                ("fr", uptr), ("pt", uptr), ("feature", uptr)]
+
+
+# every symbol include/lifcal_features.h declares
+FEATURES_PROTOTYPES = {
+    "lifcal_features_check": (C.c_int, [C.POINTER(RawDepthImage), C.POINTER(FeaturesOptions), C.POINTER(FeaturesPlan)]),
+    "lifcal_features_detect": (C.c_int, [C.POINTER(RawDepthImage), C.c_void_p, C.c_int32, C.POINTER(FeaturesOptions), C.POINTER(FeaturesList)]),
+    "lifcal_features_pattern": (C.c_int, [C.POINTER(C.c_int8)]),
+    "lifcal_features_match_check": (C.c_int, [C.POINTER(FeaturesSet), C.c_uint32, uptr, C.POINTER(MatchOptions), C.POINTER(MatchOptions)]),
+    "lifcal_features_match": (C.c_int, [C.POINTER(FeaturesSet), C.c_uint32, uptr, C.c_int32, C.POINTER(MatchOptions), C.POINTER(MatchList)]),
+    "lifcal_tracks_link": (C.c_int, [C.c_uint32, uptr, C.c_uint32, uptr, C.POINTER(C.c_uint64), uptr, uptr, C.POINTER(Tracks)]),
+}
+
 # every symbol include/lifcal_prior.h declares
 PRIOR_PROTOTYPES = {
     "lifcal_ba_check_point_priors": (C.c_int, [C.c_uint32, C.POINTER(PointPriors)]),
@@ -688,7 +729,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()) + list(TOTALFOCUS_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()) + list(TOTALFOCUS_PROTOTYPES.items()) + list(FEATURES_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args
