@@ -20,6 +20,21 @@
 
 namespace lifcal {
 
+// wave64 maximum of unsigned 64-bit words through DPP (the steps of wave_sum_dpp); the maximum ends up in lane 63
+template <int CTRL, int ROW_MASK>
+LIFCAL_DEV unsigned long long dpp_max_u64_step(unsigned long long v) {
+  const int lo = (int)(uint32_t)v, hi = (int)(uint32_t)(v >> 32);
+  const uint32_t lo2 = (uint32_t)__builtin_amdgcn_update_dpp(0, lo, CTRL, ROW_MASK, 0xf, true);
+  const uint32_t hi2 = (uint32_t)__builtin_amdgcn_update_dpp(0, hi, CTRL, ROW_MASK, 0xf, true);
+  const unsigned long long o = ((unsigned long long)hi2 << 32) | lo2;
+  return o > v ? o : v;
+}
+LIFCAL_DEV unsigned long long wave_max_u64_dpp(unsigned long long v) {
+  v = dpp_max_u64_step<0x111, 0xf>(v); v = dpp_max_u64_step<0x112, 0xf>(v); v = dpp_max_u64_step<0x114, 0xf>(v); v = dpp_max_u64_step<0x118, 0xf>(v);
+  v = dpp_max_u64_step<0x142, 0xa>(v); v = dpp_max_u64_step<0x143, 0xc>(v);
+  return v;
+}
+
 // WR = waves per role: 4 (512 threads, passes of 256 lanes, one workgroup per CU) or 2 (256 threads, passes of 128 lanes, an LDS
 // window under 80 KiB: TWO workgroups per CU, out of step with each other, so that one's latency-bound phases — pass top,
 // the single-wave factor phase, LDS-atomic emission — run under the other's observation loop).
@@ -64,6 +79,13 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
   const uint32_t ncol = 6 * nf + NC + 1, ncolp = (ncol + 15u) & ~15u;
   const uint32_t zs = ncolp + 2;
   const CamConsts c = *d.camc;
+  // The trust-region radius of the point damping, read ONCE (device LM loop: it lives in HBM).  Read where the factor uses it, the
+  // load sits under a condition and its wait in front of the merge drains the wave's whole memory counter — the Av stores of round
+  // A included — in every pass, whichever way the condition goes.
+  // WR == 2 keeps that load, and the one of the frame's live flag (below), in place: those instantiations are at the register limit
+  // and one more value carried across the loop costs them scratch.
+  constexpr bool EARLY_LOADS = WR == 4;
+  const double lm_rad = EARLY_LOADS ? lm_radius(d, radius) : 0.0;
 #ifdef LIFCAL_STAMPS
   unsigned long long st_acc[16] = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0}, st_last = 0;
   if (tid == 0 || tid == LP) { asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(st_last) :: "memory"); }
@@ -184,35 +206,60 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");     // the wave's LDS traffic of this step is done before the counter moves
     __hip_atomic_store(flag, value, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
   };
+  auto reached = [](uint32_t* flag, uint32_t need) {   // one look at a counter, the same for the whole wave; acquire as in wait_for
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP)) >= need;
+  };
   uint32_t* factor_done = (uint32_t*)(misc + 3) + 1;       // passes whose points evaluator wave 0 has factored (monotone; argued where it is published)
-  // ---- one thread per point: damp, factor U = L L^T (k_sweep2 phase 2); run by evaluator wave 0 (np <= 64) ----
-  auto factor_points = [&](uint32_t np, uint32_t p, double fsg0, double fsg1, double fsg2) {
-    if (tid < np) {
-      pidl[tid] = p;
-      double* acc = slab + tid * SLAB_STRIDE;
+  // ---- one thread per point: damp, factor U = L L^T (k_sweep2 phase 2); run by evaluator wave 0 (np <= 64), all 64 lanes active ----
+  // In two halves around publish(factor_done).  The HEAD computes what the waiters read: L^-1 into the six slab cells of the point
+  // and the rhs column of Z.  The TAIL — point index, U^-1, lam, g to HBM, the bad-U count and max |g| — is read behind barrier P4 or
+  // the T barriers only (wave 0 reaches P4 behind it) and runs from registers: it reads none of the slab cells that now hold L^-1.
+  // The bad-U count (ballot + popcount) and max |g| (DPP over the bit patterns, which order like the non-negative doubles they are:
+  // what atomicMax compared) cost ONE LDS atomic each per wave and pass instead of one per point on one word.
+  auto factor_points = [&](uint32_t np, uint32_t p, double fsg0, double fsg1, double fsg2, uint32_t passes_done) {
+    const bool live = tid < np, full = live && mode != 1;
+    double lam[3] = {0.0, 0.0, 0.0}, g0 = 0.0, g1 = 0.0, g2 = 0.0;
+    double i00 = 0.0, i11 = 0.0, i22 = 0.0, m10 = 0.0, m21 = 0.0, m20 = 0.0;
+    bool ok = true;
+    double* acc = slab + tid * SLAB_STRIDE;
+    if (full) {
       double U0 = acc[0], U1 = acc[1], U2 = acc[2], U3 = acc[3], U4 = acc[4], U5 = acc[5];
+      g0 = acc[6]; g1 = acc[7]; g2 = acc[8];
+      {
+        const double h[3] = {U0, U3, U5}, sgv[3] = {fsg0, fsg1, fsg2};
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { const double sg = sgv[k]; lam[k] = fmin(fmax(h[k] * sg * sg, d.lm_min), d.lm_max) / ((EARLY_LOADS ? lm_rad : lm_radius(d, radius)) * sg * sg); }
+      }
+      U0 += lam[0]; U3 += lam[1]; U5 += lam[2];
+      ok = U0 > 0.0;
+      i00 = rsqrt(U0);
+      const double l10 = U1 * i00, l20 = U2 * i00;
+      const double d11 = U3 - l10 * l10; ok = ok && (d11 > 0.0);
+      i11 = rsqrt(d11);
+      const double l21 = (U4 - l20 * l10) * i11;
+      const double d22 = U5 - l20 * l20 - l21 * l21; ok = ok && (d22 > 0.0);
+      i22 = rsqrt(d22);
+      m10 = -l10 * i00 * i11; m21 = -l21 * i11 * i22; m20 = -(l20 * i00 + l21 * m10) * i22;
+      if (!ok) { i00 = i11 = i22 = m10 = m21 = m20 = 0.0; }   // (the lanes of the point then add zeros to Z)
+      acc[0] = i00; acc[1] = m10; acc[2] = m20; acc[3] = i11; acc[4] = m21; acc[5] = i22;
+      double* z0 = Zd + (size_t)(3 * tid) * zs + (ncol - 1);
+      z0[0] = i00 * g0; z0[zs] = m10 * g0 + i11 * g1; z0[2 * zs] = m20 * g0 + m21 * g1 + i22 * g2;
+    }
+    // factor_done: passes whose points are factored.  Monotone, zeroed with misc; the counters are the same four with the same
+    // values as before the factor was cut in two.  Wave 0 is resident as long as any wave of the workgroup is (the early return on
+    // LM_TERMINATION is taken by the whole grid in front of everything) and gets here in every pass on every path: the halves of the
+    // factor are under `tid < np` and the lanes' rounds under `cnt > 0`, the counters are not.  Every evaluator wave, wave 0
+    // included, bumps eval_done right behind its own round A and before it waits for or looks at anything (deterministic mode:
+    // behind its turn of round A, turns that wave 0 opens itself and that are handed on unconditionally); the only BLOCKING wait on
+    // wave 0's way here is the one on eval_done; no wave waits for factor_done in front of its eval_done bump, so the two counters
+    // cannot wait for each other.  np of 1 or 64, idle lanes and fixed frames change lane masks only.
+    publish(factor_done, passes_done);   // (behind s_waitcnt lgkmcnt(0): L^-1 in the slab and the rhs column of Z are written)
+    if (live) {
+      pidl[tid] = p;
       if (mode == 1) {
         double* ga = d.ptacc + (size_t)p * 36;
-        store_stream(ga, U0); store_stream(ga + 3, U3); store_stream(ga + 5, U5);
+        store_stream(ga, acc[0]); store_stream(ga + 3, acc[3]); store_stream(ga + 5, acc[5]);   // (mode 1 has no head: the slab holds U)
       } else {
-        const double g0 = acc[6], g1 = acc[7], g2 = acc[8];
-        double lam[3];
-        {
-          const double h[3] = {U0, U3, U5}, sgv[3] = {fsg0, fsg1, fsg2};
-#pragma unroll
-          for (int k = 0; k < 3; ++k) { const double sg = sgv[k]; lam[k] = fmin(fmax(h[k] * sg * sg, d.lm_min), d.lm_max) / (lm_radius(d, radius) * sg * sg); }
-        }
-        U0 += lam[0]; U3 += lam[1]; U5 += lam[2];
-        bool ok = U0 > 0.0;
-        double i00 = rsqrt(U0);
-        const double l10 = U1 * i00, l20 = U2 * i00;
-        const double d11 = U3 - l10 * l10; ok = ok && (d11 > 0.0);
-        double i11 = rsqrt(d11);
-        const double l21 = (U4 - l20 * l10) * i11;
-        const double d22 = U5 - l20 * l20 - l21 * l21; ok = ok && (d22 > 0.0);
-        double i22 = rsqrt(d22);
-        double m10 = -l10 * i00 * i11, m21 = -l21 * i11 * i22, m20 = -(l20 * i00 + l21 * m10) * i22;
-        if (!ok) { i00 = i11 = i22 = m10 = m21 = m20 = 0.0; atomicAdd(misc + 1, 1.0); }   // (the lanes of the point then add zeros to Z)
         double* gu = d.Uinv + 9 * (size_t)p;
         const double v00 = i00 * i00 + m10 * m10 + m20 * m20, v01 = m10 * i11 + m20 * m21, v02 = m20 * i22;
         const double v11 = i11 * i11 + m21 * m21, v12 = m21 * i22, v22 = i22 * i22;
@@ -226,11 +273,15 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
 #pragma unroll
         for (int k = 0; k < 3; ++k) store_stream(gl + k, lam[k]);
         store_stream(ga, g0); store_stream(ga + 1, g1); store_stream(ga + 2, g2);
-        const double gm = fmax(fabs(g0), fmax(fabs(g1), fabs(g2)));
-        atomicMax((unsigned long long*)(misc + 2), (unsigned long long)__double_as_longlong(gm));
-        acc[0] = i00; acc[1] = m10; acc[2] = m20; acc[3] = i11; acc[4] = m21; acc[5] = i22;
-        double* z0 = Zd + (size_t)(3 * tid) * zs + (ncol - 1);
-        z0[0] = i00 * g0; z0[zs] = m10 * g0 + i11 * g1; z0[2 * zs] = m20 * g0 + m21 * g1 + i22 * g2;
+      }
+    }
+    if (mode != 1) {
+      const unsigned long long nbad = (unsigned long long)__popcll(__ballot(full && !ok));
+      const double gm = fmax(fabs(g0), fmax(fabs(g1), fabs(g2)));   // (0, the neutral element, on the lanes without a point)
+      const unsigned long long gmax = wave_max_u64_dpp((unsigned long long)__double_as_longlong(gm));
+      if (lane == 63) {
+        atomicMax((unsigned long long*)(misc + 2), gmax);
+        if (nbad != 0) atomicAdd(misc + 1, (double)nbad);
       }
     }
   };
@@ -459,11 +510,15 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
       // `tid < np`, they make the compiler drain the counter, the kernel's write-through stores included, in the Z phase and in
       // emit_tile).
       const double fsg0 = d.sigP[3 * (size_t)fp], fsg1 = d.sigP[3 * (size_t)fp + 1], fsg2 = d.sigP[3 * (size_t)fp + 2];
+      // The frame's live flag travels with them: loaded at the top of round B, behind the streaming stores of round A and of the factor,
+      // its wait was a wait for those stores (the memory counter retires in order).  (Every lane's frame exists: the pass top reads its row.)
+      uint32_t flive = 1;
+      if constexpr (EARLY_LOADS) flive = d.frame_live[fr];
       STAMP(7);
       lds_barrier();                                                                                    // ---- barrier P2a: every accumulator has taken its last step
       if (mode == 0) zero_zd(krows);
       lds_barrier();                                                                                    // ---- barrier P2
-      asm volatile("" :: "v"(fsg0), "v"(fsg1), "v"(fsg2));
+      asm volatile("" :: "v"(fsg0), "v"(fsg1), "v"(fsg2), "v"(flive));
       // The emission runs in two rounds around the factor phase.  Round A: U and g of the lane's point, all the factor phase
       // reads.  Round B: the frame-level values, then, once the point is factored, the lane's share of Z = L^-1 W for its six pose
       // columns: the lane applies L^-1 to W while it still holds it, and the Z phase keeps the camera columns only.  L^-1 is
@@ -501,66 +556,78 @@ __global__ __launch_bounds__(128 * WR, 2) void k_sweep3(Dev d, double radius, in
       // evaluator waves through an LDS counter instead of a workgroup barrier, so it runs under round B of the other evaluator
       // waves and under the longer emission of the accumulator waves; everybody meets again at barrier P4.
       // (options.deterministic: eval_done is bumped behind the wave's turn of round A, so the same wait serves.)
-      // Wave 0 factors BETWEEN its rounds.  With its frame-level values in front of the factor (every wave in one order: A, frame
-      // values, factor on wave 0, Z) the wait for eval_done shrinks from 10.9 k to 2.3 k cycles per block, the emission grows by as
-      // much and the step measures the same (profiles/sweep_zfused/).
+      // Wave 0 does not stand idle until the other evaluator waves have left round A: it LOOKS at eval_done (one acquire load, a
+      // wave-uniform branch) right behind its own bump and again behind the 21 values of the 6x6 block, works on its frame-level
+      // values in between, factors as soon as a look finds the counter complete, and blocks only behind the last of the 27 values.
+      // Both fixed orders — the factor between the rounds, the frame-level values in front of it — measured the same
+      // (profiles/sweep_zfused/): either wave 0 idled or the factor started later for everybody.
+      // options.deterministic keeps its order (A of all waves, factor, B of all waves): there the first look is the blocking wait.
+      // The factor is inlined at two sites, the last six frame-level values (the smaller body) at two as well.
       asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
       if (lane == 0) __hip_atomic_fetch_add(eval_done, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
       ++passes_done;
+      bool factored = true;   // (waves 1..WR-1 have nothing to factor)
       if (w == 0) {
-        wait_for(eval_done, (uint32_t)WR * passes_done);
+        if (det) wait_for(eval_done, (uint32_t)WR * passes_done);
+        factored = det || reached(eval_done, (uint32_t)WR * passes_done);
         STAMP(1);
-        factor_points(np, fp, fsg0, fsg1, fsg2);
-        // factor_done: passes whose points are factored.  Monotone, zeroed with misc.  Wave 0 is resident as long as any wave of
-        // the workgroup is (the early return on LM_TERMINATION is taken by the whole grid in front of everything), it gets here
-        // in every pass on every path — the factor's body is under `tid < np` and the lanes' round A under `cnt > 0`, the
-        // counters are not — and its only wait on the way is eval_done, which every evaluator wave bumps right behind its own
-        // round A without waiting for anybody (deterministic mode: behind its turn of round A, turns that wave 0 opens itself
-        // and that are handed on unconditionally).  No wave waits for factor_done in front of its eval_done bump, so the two
-        // counters cannot wait for each other; np of 1 or 64, idle lanes and fixed frames change lane masks only.
-        publish(factor_done, passes_done);   // (behind s_waitcnt lgkmcnt(0): L^-1 in the slab and the rhs column of Z are written)
-        STAMP(2);
+        if (factored) { factor_points(np, fp, fsg0, fsg1, fsg2, passes_done); STAMP(2); }
       }
       // ---- round B ----
       if (det) wait_for(turn, my_turn + (uint32_t)WR);
-      const bool fpose = cnt > 0 && d.frame_live[fr] != 0;   // 0: the pose of this frame is held constant (lifcal_ba_set_fixed_frames): no pose columns
+      if constexpr (!EARLY_LOADS) { if (cnt > 0) flive = d.frame_live[fr]; }
+      const bool fpose = cnt > 0 && flive != 0;   // 0: the pose of this frame is held constant (lifcal_ba_set_fixed_frames): no pose columns
       double AG[3][3];
 #pragma unroll
       for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) AG[i][j] = Am[i][0] * Gr[0][j] + Am[i][1] * Gr[1][j] + Am[i][2] * Gr[2][j];
+      RunMask rm = run_masks(cnt, lf);   // (idle lanes: no match, no head)
+      rm.head = rm.head && fpose;
+      double* fr_acc = Fr + lf;
       if (cnt > 0) {
         double GAG[3][3];
 #pragma unroll
         for (int i = 0; i < 3; ++i)
 #pragma unroll
           for (int j = 0; j < 3; ++j) GAG[i][j] = Gr[0][i] * AG[0][j] + Gr[1][i] * AG[1][j] + Gr[2][i] * AG[2][j];
-        RunMask rm = run_masks(cnt, lf);
-        rm.head = rm.head && fpose;
-        double* fr_acc = Fr + lf;
-        {
-          int vi = 0;
+        int vi = 0;
 #pragma unroll
-          for (int a = 0; a < 6; ++a)
+        for (int a = 0; a < 6; ++a)
 #pragma unroll
-            for (int bb = 0; bb <= a; ++bb) {
-              double v;
-              if (a < 3) v = GAG[a][bb]; else if (bb < 3) v = AG[a - 3][bb]; else v = Am[a - 3][bb - 3];
-              v = run_sum(v, rm);
-              if (rm.head) atomicAdd(fr_acc + (size_t)vi * frs, v);
-              ++vi;
-            }
+          for (int bb = 0; bb <= a; ++bb) {
+            double v;
+            if (a < 3) v = GAG[a][bb]; else if (bb < 3) v = AG[a - 3][bb]; else v = Am[a - 3][bb - 3];
+            v = run_sum(v, rm);
+            if (rm.head) atomicAdd(fr_acc + (size_t)vi * frs, v);
+            ++vi;
+          }
+      }
+      auto frame_gradient = [&]() {   // the last six frame-level values
+        if (cnt > 0) {
 #pragma unroll
           for (int a = 0; a < 3; ++a) { const double v = run_sum(Gr[0][a] * bv[0] + Gr[1][a] * bv[1] + Gr[2][a] * bv[2], rm); if (rm.head) atomicAdd(fr_acc + (size_t)(21 + a) * frs, v); }
 #pragma unroll
           for (int a = 0; a < 3; ++a) { const double v = run_sum(bv[a], rm); if (rm.head) atomicAdd(fr_acc + (size_t)(24 + a) * frs, v); }
         }
+      };
+      bool gradient_done = false;
+      if (!factored) {   // wave 0, plain mode, the counter was not complete at the first look
+        if (!reached(eval_done, (uint32_t)WR * passes_done)) {
+          frame_gradient(); gradient_done = true;
+          STAMP(6);
+          wait_for(eval_done, (uint32_t)WR * passes_done);   // the only blocking wait on wave 0's way to the publish, as before
+          STAMP(1);
+        } else STAMP(6);
+        factor_points(np, fp, fsg0, fsg1, fsg2, passes_done);
+        STAMP(2);
       }
+      if (!gradient_done) frame_gradient();
       if (mode == 0) {
         // the points of this pass are factored: the slab holds L^-1 (zeros where U was not positive definite).
         // options.deterministic: the lanes add W itself, times the identity (exact), and the Z phase transforms the sums as it always
         // did (see z_phase), so the mode's results keep their bits; the wait is not needed then.
-        if (!det) wait_for(factor_done, passes_done);
+        if (!det && w != 0) wait_for(factor_done, passes_done);   // (wave 0 wrote L^-1 itself: its LDS traffic stays in order)
         if (fpose) {
           double i00 = 1.0, m10 = 0.0, m20 = 0.0, i11 = 1.0, m21 = 0.0, i22 = 1.0;
           if (!det) { i00 = acc[0]; m10 = acc[1]; m20 = acc[2]; i11 = acc[3]; m21 = acc[4]; i22 = acc[5]; }
