@@ -96,7 +96,7 @@ def slot_target(s, j, span):
     return s + j - span + (1 if j >= span else 0)
 
 
-def _pair_pixels(raw, cam, config, spx, fts, s, t, tol_iv):
+def _pair_pixels(raw, cam, config, spx, fts, s, t, tol_iv, spy=None):
     """One source map against one target.  For every pixel of s (flattened row-major): class, e, the sampled target pixel
     (flattened index, -1 without one) and its v_obs."""
     count, H, W = raw.shape
@@ -107,9 +107,9 @@ def _pair_pixels(raw, cam, config, spx, fts, s, t, tol_iv):
     if len(idx) == 0:
         return cls, e_all, tpix, vobs_all
     rows, cols = idx // W, idx % W
-    p_s = dr.back_project_cam(cols, rows, v_s[idx], cam, config, spx)
+    p_s = dr.back_project_cam(cols, rows, v_s[idx], cam, config, spx, spy=spy)
     p_t = to_camera(pair_transform(fts[s], fts[t]), p_s)         # the 12 entries are laid out like a frame table
-    x_t, y_t, v_pred, okf = forward_exact(p_t, cam, config, spx)
+    x_t, y_t, v_pred, okf = forward_exact(p_t, cam, config, spx, spy=spy)
     with np.errstate(invalid="ignore"):
         fx = x_t + 0.5; fy = y_t + 0.5
         okf = okf & (fx > -1.0e9) & (fx < 1.0e9) & (fy > -1.0e9) & (fy < 1.0e9)
@@ -133,7 +133,7 @@ def _pair_pixels(raw, cam, config, spx, fts, s, t, tol_iv):
     return cls, e_all, tpix, vobs_all
 
 
-def check_ref(raw, cam, config, spx, frame, views, span=1, tol_iv=4 * STEP, details=False):
+def check_ref(raw, cam, config, spx, frame, views, span=1, tol_iv=4 * STEP, details=False, spy=None):
     """lifcal_depth_check_maps on host arrays: raw (count, H, W) uint16.  Returns (support, conflict, pair) with pair a
     (count, 2 span) array of PAIR_DTYPE; details=True adds {(s, t): (cls, e, target pixel, v_obs)} and the distance of the nearest
     |e| to the threshold.  sum_e / sum_e2 are plain numpy sums: the comparison is at 1e-12, not bitwise."""
@@ -150,7 +150,7 @@ def check_ref(raw, cam, config, spx, frame, views, span=1, tol_iv=4 * STEP, deta
             t = slot_target(s, j, span)
             if t < 0 or t >= count:
                 continue
-            cls, e, tpix, v_obs = _pair_pixels(raw, cam, config, spx, fts, s, t, tol_iv)
+            cls, e, tpix, v_obs = _pair_pixels(raw, cam, config, spx, fts, s, t, tol_iv, spy=spy)
             con = cls == CONSISTENT
             support[s] += con.astype(np.uint8); conflict[s] += (cls == VIOLATION).astype(np.uint8)
             row = pair[s, j]
@@ -250,7 +250,7 @@ def scene_surface(x, y):
     return np.where(box, 480.0, plane)
 
 
-def render_maps(cam, views, W, H):
+def render_maps(cam, views, W, H, spy=None):
     """One map per pose.  Every pixel is rendered by bisection on v until the back-projected world point lies on the surface
     (60 halvings: to the last bit), then encoded with dr.encode_vdepth.  A ray that crosses the box's edge finds the side wall."""
     rows, cols = np.mgrid[0:H, 0:W]
@@ -260,7 +260,7 @@ def render_maps(cam, views, W, H):
         ft = frame_table(views[m])
 
         def gap(v):
-            p_w = to_world(ft, dr.back_project_cam(cols, rows, v, cam, CONFIG_FIX, SPX_FIX))
+            p_w = to_world(ft, dr.back_project_cam(cols, rows, v, cam, CONFIG_FIX, SPX_FIX, spy=spy))
             return p_w[:, 2] - scene_surface(p_w[:, 0], p_w[:, 1])
         lo = np.full(len(cols), 2.0); hi = np.full(len(cols), 20.0)   # Z falls as v rises: gap(lo) > 0 > gap(hi)
         assert np.all(gap(lo) > 0) and np.all(gap(hi) < 0)

@@ -34,6 +34,40 @@ def problem(sc, initial=True):
     return capi.ProblemArrays.from_scene(sc, initial=initial)
 
 
+def anisotropic_scene(sc, a):
+    """A copy of the scene `sc` with the y pixel pitch multiplied by `a` (attribute spy = a spx) and every raw y coordinate divided
+    by it: v, mcy and the raw principal point craw_y = (cam[4] + 0.5) scale - 0.5 (cam_gt[4], cam0[4] and the bounds on cam[4] are
+    re-expressed so that craw_y' = craw_y / a).  The model sees the same metric sensor, so r_x' = r_x and r_y' = r_y / a for every
+    observation (tests/test_off_defaults_cpu.py)."""
+    import dataclasses
+    s = float(sc.scale)
+
+    def fold(cam):   # monotone in cam[4], keeps +-inf
+        if cam is None:
+            return None
+        out = np.array(cam, float)
+        out[4] = (((out[4] + 0.5) * s - 0.5) / a + 0.5) / s - 0.5
+        return out
+
+    out = dataclasses.replace(sc, v=sc.v / a, mcy=sc.mcy / a, cam_gt=fold(sc.cam_gt), cam0=fold(sc.cam0), lower=fold(sc.lower), upper=fold(sc.upper))
+    out.spy = a * sc.spx
+    return out
+
+
+def spy_of(sc):
+    """the y pixel pitch of a scene for the `spy` argument of the library's calls and of capi.ProblemArrays: the one
+    anisotropic_scene gave it, None (the x pitch) for a scene as scene.make_scene returns it"""
+    return getattr(sc, "spy", None)
+
+
+def anisotropic(sc, a, initial=True):
+    """the problem of anisotropic_scene(sc, a)"""
+    an = anisotropic_scene(sc, a)
+    pa = problem(an, initial)
+    pa.struct.spy = spy_of(an)
+    return pa
+
+
 def bounded_problem(sc):
     """the recalib pattern with a tight box: fL and B fixed, bL0 / cx / cy boxed so closely that the projected LM step
     fails ceres' Armijo test and TrustRegionMinimizer::DoLineSearch backtracks (checked on the oracle with LO_DEBUG_LS=1)"""

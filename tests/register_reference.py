@@ -20,19 +20,20 @@ from tests import start_reference as sr
 MODEL_BITS = 0xA07   # nRadial, tangential, ROBUST, ML_CENTER_ADJ
 
 
-def _groups(arm, cam, u, v, mcx, mcy, pt, fr, n_frames, n_points, config, spx, scale, gate_px):
+def _groups(arm, cam, u, v, mcx, mcy, pt, fr, n_frames, n_points, config, spx, scale, gate_px, spy=None):
     if arm == "cpu":
-        return sr.group_rows(cam, u, v, mcx, mcy, pt, fr, config, spx, scale, gate_px=gate_px)[0]
+        return sr.group_rows(cam, u, v, mcx, mcy, pt, fr, config, spx, scale, spy=spy, gate_px=gate_px)[0]
     from lifcal_amd import startPoses
-    return startPoses(cam, np.zeros((n_points, 3)), u, v, mcx, mcy, pt, fr, n_frames, config, spx, scale, gatePx=gate_px, wantGroups=True).groups
+    return startPoses(cam, np.zeros((n_points, 3)), u, v, mcx, mcy, pt, fr, n_frames, config, spx, scale, spy=spy, gatePx=gate_px, wantGroups=True).groups
 
 
 class _Solver:
     """one LM solve per frame (over its observations of mapped points) or per point (over its observations in registered frames)"""
 
-    def __init__(self, arm, cam, u, v, mcx, mcy, pt, fr, config, spx, scale, options):
+    def __init__(self, arm, cam, u, v, mcx, mcy, pt, fr, config, spx, scale, options, spy=None):
         self.arm, self.cam, self.obs, self.pt, self.fr = arm, cam, (u, v, mcx, mcy), pt, fr
         self.config, self.spx, self.scale, self.options = config, spx, scale, options
+        self.spy = spy   # None: spx
 
     def poses(self, frames, views, pts, mapped):
         """refines views[frames] in place; returns {frame: (final_cost, iterations, termination)}"""
@@ -42,7 +43,7 @@ class _Solver:
             for f in frames:
                 m = (self.fr == f) & mapped[self.pt]
                 pa = capi.ProblemArrays(*(a[m] for a in self.obs), self.pt[m], np.zeros(int(m.sum()), np.uint32), self.cam, views[f].copy(), P,
-                                        self.spx, self.scale, (self.config & MODEL_BITS) | 0x100, fixed_mask=0x1FFFF)
+                                        self.spx, self.scale, (self.config & MODEL_BITS) | 0x100, spy=self.spy, fixed_mask=0x1FFFF)
                 s = oracle.solve(pa, self.options)
                 views[f] = pa.views
                 out[f] = (s.final_cost, s.iterations, s.termination)
@@ -51,7 +52,7 @@ class _Solver:
         frames = np.asarray(frames)
         m = np.isin(self.fr, frames) & mapped[self.pt]
         local = np.zeros(int(self.fr.max()) + 1, np.uint32); local[frames] = np.arange(len(frames))
-        res = resectFrames(self.cam, P, *(a[m] for a in self.obs), self.pt[m], local[self.fr[m]], views[frames], self.config, self.spx, self.scale, options=self.options)
+        res = resectFrames(self.cam, P, *(a[m] for a in self.obs), self.pt[m], local[self.fr[m]], views[frames], self.config, self.spx, self.scale, spy=self.spy, options=self.options)
         views[frames] = res.views
         for k, f in enumerate(frames):
             out[int(f)] = (float(res.final_cost[k]), int(res.iterations[k]), int(res.termination[k]))
@@ -67,7 +68,7 @@ class _Solver:
                 for k in points:
                     m = (self.pt == k) & registered[self.fr]
                     pa = capi.ProblemArrays(*(a[m] for a in self.obs), np.zeros(int(m.sum()), np.uint32), self.fr[m], self.cam, V, pts[k].copy(),
-                                            self.spx, self.scale, (self.config & MODEL_BITS) | 0x500, fixed_mask=0x1FFFF)
+                                            self.spx, self.scale, (self.config & MODEL_BITS) | 0x500, spy=self.spy, fixed_mask=0x1FFFF)
                     c0 = oracle.cost(pa)
                     if not np.isfinite(c0):
                         out[k] = (c0, 0, 0)
@@ -82,7 +83,7 @@ class _Solver:
         points = np.asarray(points)
         m = np.isin(self.pt, points) & registered[self.fr]
         local = np.zeros(int(self.pt.max()) + 1, np.uint32); local[points] = np.arange(len(points))
-        res = intersectPoints(self.cam, V, *(a[m] for a in self.obs), local[self.pt[m]], self.fr[m], pts[points], self.config, self.spx, self.scale, options=self.options)
+        res = intersectPoints(self.cam, V, *(a[m] for a in self.obs), local[self.pt[m]], self.fr[m], pts[points], self.config, self.spx, self.scale, spy=self.spy, options=self.options)
         pts[points] = res.pts
         for j, k in enumerate(points):
             out[int(k)] = (float(res.final_cost[j]), int(res.iterations[j]), int(res.termination[j]))
@@ -90,7 +91,7 @@ class _Solver:
 
 
 def register(arm, cam, u, v, mcx, mcy, pt, fr, n_frames, n_points, config, spx, scale, gate_px=1.0, min_shared=6, anchor_frame=-1, anchor_view=None,
-             max_rounds=0, options=None):
+             max_rounds=0, options=None, spy=None):
     """the chain; returns a namespace with views (F, 6) and pts (P, 3) (NaN where not written), the group table, per frame status,
     round, n_obs, n_obs_used, n_groups, n_used, n_shared and last (final_cost, iterations, termination), per point status, round,
     n_obs, n_obs_used, n_frames_used and last, and anchor_frame, n_rounds"""
@@ -102,7 +103,7 @@ def register(arm, cam, u, v, mcx, mcy, pt, fr, n_frames, n_points, config, spx, 
     out.f_status, out.f_round = np.where(out.f_n_obs > 0, 2, 1), np.full(F, -1)
     out.p_status, out.p_round = np.where(out.p_n_obs > 0, 2, 1), np.full(P, -1)
     out.f_n_shared, out.f_last, out.p_last = np.zeros(F, np.int64), {}, {}
-    out.groups = groups = _groups(arm, cam, u, v, mcx, mcy, pt, fr, F, P, config, spx, scale, gate_px) if len(u) else np.zeros(0, capi.START_GROUP_DTYPE)
+    out.groups = groups = _groups(arm, cam, u, v, mcx, mcy, pt, fr, F, P, config, spx, scale, gate_px, spy) if len(u) else np.zeros(0, capi.START_GROUP_DTYPE)
     used = groups[groups["status"] == 0]           # (ascending (fr, pt) order)
     out.f_n_groups, out.f_n_used = np.bincount(groups["fr"], minlength=F), np.bincount(used["fr"], minlength=F)
     registered, mapped = np.zeros(F, bool), np.zeros(P, bool)
@@ -118,7 +119,7 @@ def register(arm, cam, u, v, mcx, mcy, pt, fr, n_frames, n_points, config, spx, 
 
     if len(used) == 0:
         return finish()
-    solver = _Solver(arm, np.asarray(cam, np.float64), u, v, mcx, mcy, pt, fr, config, spx, scale, options)
+    solver = _Solver(arm, np.asarray(cam, np.float64), u, v, mcx, mcy, pt, fr, config, spx, scale, options, spy)
     views, pts = out.views, out.pts
 
     def extend(r):

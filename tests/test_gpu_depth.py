@@ -160,14 +160,14 @@ def dense_fixture(W=250, H=37, count=3, seed=5):
     return raw
 
 
-def dense_reference(raw, cam, config, dtype=np.float64):
+def dense_reference(raw, cam, config, dtype=np.float64, spy=None):
     count, H, W = raw.shape
     v = dr.decode_direct(raw)
     ok = np.isfinite(v)
     rows, cols = np.mgrid[0:H, 0:W]
     cols = np.broadcast_to(cols, raw.shape); rows = np.broadcast_to(rows, raw.shape)
     out = np.full(raw.shape + (3,), np.nan, dtype)
-    out[ok] = dr.back_project_cam(cols[ok], rows[ok], v[ok], cam, config, SPX, dtype=dtype)
+    out[ok] = dr.back_project_cam(cols[ok], rows[ok], v[ok], cam, config, SPX, spy=spy, dtype=dtype)
     return out, v, ok
 
 
@@ -238,6 +238,68 @@ def test_dense_fp32_option_against_the_float32_restatement(built):
         print(f"config {config:#x}: float32 restatement vs fp64 {dev_ref:.3e}; fp32 kernel vs float32 restatement {dev:.3e}, vs fp64 {dev64:.3e}")
         assert dev <= 4.0 * dev_ref
         assert np.array_equal(r.z[ok], r.xyz[ok][:, 2])
+
+
+def test_a_y_pixel_pitch_of_its_own(built):
+    """spy = 1.25 spx through backProjectPoints (with its Jacobian), projectPoints and backProjectMaps in both evaluation options, each
+    at the bar its test above holds at spy = spx; the restatement at spy = spx, which a pitch read from the x slot computes, lies
+    far outside every one of them"""
+    from tests import depth_views_reference as vr
+    spy = 1.25 * SPX
+    rs = np.random.default_rng(41)
+    n = 3000
+    for config in (0x6, 0x5, 0x0):
+        cam = camera_for(DEFAULT, config)
+        x = rs.uniform(0, 1023, n); y = rs.uniform(0, 1023 / 1.25, n); v = rs.uniform(2.3, 12.0, n)
+        r = depth.backProjectPoints(x, y, v, cam, config, SPX, spy=spy, want_jacobian=True)
+        want, iso = dr.back_project_cam(x, y, v, cam, config, SPX, spy=spy), dr.back_project_cam(x, y, v, cam, config, SPX)
+        assert np.array_equal(r.p_c, want)
+        moved = np.abs(want - iso) / want[:, 2:3]
+        assert np.median(moved[:, 1]) > 1e-3                            # the y pitch moves Y of every point (and, through r^2, X where there is distortion)
+        J, dv = dr.jacobian_complex_step(x, y, v, cam, config, SPX, spy=spy)
+        J_iso, _ = dr.jacobian_complex_step(x, y, v, cam, config, SPX)
+        row = np.linalg.norm(J, axis=2, keepdims=True)
+        err, err_v = np.max(np.abs(r.jac - J) / row), np.max(np.abs(r.dpc_dv - dv) / np.linalg.norm(dv, axis=1, keepdims=True))
+        wrong = np.median(np.max(np.abs(J_iso - J) / row, axis=(1, 2)))
+        print(f"config {config:#x}: Y moves by {np.median(moved[:, 1]):.2e} of Z; jacobian {err:.2e} of the row norm, d/dv {err_v:.2e}; the one at spy = spx {wrong:.2e}")
+        assert err < 1e-9 and err_v < 1e-9 and wrong > 1e-3
+        # the forward model and the round trip
+        cam_rt = camera_for(dr.CAM_ROUND_TRIP, config)
+        vv = rs.uniform(2.0, 20.0, n)
+        b = cam_rt[1] + vv * cam_rt[2]
+        Z = cam_rt[0] * b / (b - cam_rt[0])
+        rad = 5.6 * np.sqrt(rs.uniform(0, 1, n)); ang = rs.uniform(0, 2 * np.pi, n)
+        p = np.stack([rad * np.cos(ang) / cam_rt[1] * Z, rad * np.sin(ang) / cam_rt[1] * Z, Z], -1)
+        xe, ye, ve, ok = vr.forward_exact(p, cam_rt, config, SPX, spy=spy)
+        _, ye_iso, _, _ = vr.forward_exact(p, cam_rt, config, SPX)
+        f = depth.projectPoints(p, cam_rt, config, SPX, spy=spy)
+        assert np.all(ok) and f.n_invalid == 0
+        assert np.array_equal(f.x, xe) and np.array_equal(f.y, ye) and np.array_equal(f.vdepth, ve)
+        assert np.median(np.abs(ye - ye_iso)) > 1.0                     # pixels
+        xv, yv, v2 = dr.forward_ref(p, cam_rt, config, SPX, spy=spy)
+        back = depth.backProjectPoints(xv, yv, v2, cam_rt, config, SPX, spy=spy).p_c
+        rt = np.max(np.abs(back - p) / p[:, 2:3])
+        print(f"config {config:#x}: GPU round trip {rt:.3e} of Z")
+        assert rt < 1e-13
+    # dense, fp64 bit for bit and the fp32 option at four times the float32 restatement's own deviation
+    raw = dense_fixture(W=250, H=37, count=2, seed=12)
+    for config in (0x6, 0x0):
+        cam = camera_for(DEFAULT, config)
+        ref64, v, ok = dense_reference(raw, cam, config, spy=spy)
+        ref32, _, _ = dense_reference(raw, cam, config, dtype=np.float32, spy=spy)
+        iso64, _, _ = dense_reference(raw, cam, config)
+        Z = ref64[ok][:, 2:3]
+        assert np.median(np.abs(ref64[ok] - iso64[ok])[:, 1:2] / Z) > 1e-4
+        dev_ref = np.max(np.abs(ref32[ok].astype(np.float64) - ref64[ok]) / Z)
+        with depth.DepthMaps(raw.shape[2], raw.shape[1], 2) as dm:
+            dm.setMaps(raw)
+            d = dm.backProjectMaps(cam, config, SPX, spy=spy, out_double=True, want_z=True)
+            r32 = dm.backProjectMaps(cam, config, SPX, spy=spy, eval=1)
+        assert np.array_equal(d.xyz, ref64, equal_nan=True) and np.array_equal(d.z, ref64[..., 2], equal_nan=True) and d.n_invalid == int((~ok).sum())
+        dev = np.max(np.abs(r32.xyz[ok].astype(np.float64) - ref32[ok].astype(np.float64)) / Z)
+        wrong = np.max(np.abs(iso64[ok] - ref64[ok]) / Z)
+        print(f"config {config:#x}: dense fp32 kernel vs float32 restatement {dev:.3e} (bar {4.0 * dev_ref:.3e}); the restatement at spy = spx {wrong:.3e}")
+        assert dev <= 4.0 * dev_ref and wrong > 100.0 * dev_ref
 
 
 def test_dense_world_coordinates(built):

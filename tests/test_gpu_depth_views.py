@@ -106,6 +106,26 @@ def test_check_maps_matches_the_restatement(maps, span):
     assert only.support is None and np.array_equal(only.conflict, conflict) and only.pair.tobytes() == r.pair.tobytes()
 
 
+def test_check_maps_with_a_y_pixel_pitch_of_its_own(built):
+    """The fixture's scene rendered and cross-checked with spy = 1.25 spx: the maps are consistent with that pitch and with no other,
+    so the restatement at spy = spx (what a pitch read from the x slot computes) classes a tenth of the pixels differently, where
+    the comparison is exact"""
+    spy = 1.25 * SPX
+    cam, views = vr.fixture_camera(), vr.fixture_views()
+    raw = vr.render_maps(cam, views, vr.W_FIX, vr.H_FIX, spy=spy)
+    support, conflict, pair, _, nearest = vr.check_ref(raw, cam, CFG, SPX, FRAMES, views, 1, TOL * vr.STEP, details=True, spy=spy)
+    iso_support, _, iso_pair = vr.check_ref(raw, cam, CFG, SPX, FRAMES, views, 1, TOL * vr.STEP)
+    n_con, n_cmp, n_iso = int(pair["n_consistent"].sum()), int(pair["n_compared"].sum()), int(iso_pair["n_consistent"].sum())
+    print(f"spy = 1.25 spx: {n_con} of {n_cmp} compared pixels consistent (at spy = spx: {n_iso}), nearest |e| to the threshold {nearest:.2e}")
+    assert nearest > 1e-9 and n_con > 0.8 * n_cmp and n_iso < n_con - 1000 and np.mean(iso_support != support) > 0.05
+    with depth.DepthMaps(vr.W_FIX, vr.H_FIX, vr.N_FIX) as dm:
+        dm.setMaps(raw)
+        r = dm.checkMaps(cam, CFG, SPX, FRAMES, views, span=1, tol_steps=TOL, spy=spy)
+    assert np.array_equal(r.support, support) and np.array_equal(r.conflict, conflict)
+    assert_pairs_equal(r.pair, pair)
+    assert np.allclose(r.rms_steps(), vr.rms_steps(pair), rtol=1e-9, equal_nan=True)
+
+
 # ------------------------------------------------------------------------------------------------ 3. shapes
 def test_check_maps_shapes(built):
     raw, cam, views = vr.views_fixture()

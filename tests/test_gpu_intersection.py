@@ -23,7 +23,8 @@ import pytest
 
 import oracle
 from lifcal_amd import BundleAdjustment, _capi as capi, intersectPoints, scene
-from tests.helpers import S, scaled_max_err, vec_err
+from tests import off_defaults as od
+from tests.helpers import S, anisotropic_scene, spy_of, scaled_max_err, vec_err
 
 pytestmark = pytest.mark.gpu
 
@@ -53,13 +54,13 @@ def intersect(sc, keep=None, options=None, order=None, pts0=None, pt=None):
     points = sc.pt[idx] if pt is None else pt
     p0 = sc.pts0 if pts0 is None else pts0
     return intersectPoints(sc.cam_gt, sc.views_gt, sc.u[idx], sc.v[idx], sc.mcx[idx], sc.mcy[idx], points, sc.fr[idx], p0, sc.config, sc.spx, sc.scale,
-                           options=options)
+                           spy=spy_of(sc), options=options)
 
 
 def one_point_problem(sc, k, keep, point):
     m = (sc.pt == k) if keep is None else ((sc.pt == k) & keep)
     return capi.ProblemArrays(sc.u[m], sc.v[m], sc.mcx[m], sc.mcy[m], np.zeros(int(m.sum()), np.uint32), sc.fr[m], sc.cam_gt, sc.views_gt, point,
-                              sc.spx, sc.scale, sc.config | 0x500, fixed_mask=0x1FFFF)
+                              sc.spx, sc.scale, sc.config | 0x500, spy=spy_of(sc), fixed_mask=0x1FFFF)
 
 
 def block_sums(sc, pa, point, loss_scale):
@@ -67,7 +68,8 @@ def block_sums(sc, pa, point, loss_scale):
     views = np.asarray(sc.views_gt).reshape(-1, 6)
     H, g = np.zeros((3, 3)), np.zeros(3)
     for i in range(pa.struct.n_obs):
-        r, J = oracle.residual_block(sc.config | 0x500, 3, sc.cam_gt, views[pa.fr[i]], point, pa.u[i], pa.v[i], pa.mcx[i], pa.mcy[i], sc.spx, sc.scale)
+        r, J = oracle.residual_block(sc.config | 0x500, 3, sc.cam_gt, views[pa.fr[i]], point, pa.u[i], pa.v[i], pa.mcx[i], pa.mcy[i], sc.spx, sc.scale,
+                                     spy=spy_of(sc))
         J = J[:, 23:26]
         if sc.config & 0x200:
             w = 1.0 / np.sqrt(1.0 + float(r @ r) / loss_scale ** 2)
@@ -177,6 +179,61 @@ def test_rejected_steps_walk_the_decrease_factor_path(built):
     print(f"far start against pts0: points {np.max(np.abs(d)):.2e} mm apart, 1/2 d^T H d {dh:.2e} of the cost, final costs {dc:.2e} relative")
     assert dc <= 1e-4
     assert dh <= 4e-4
+
+
+# away from the default scalars and options (tests/off_defaults.py): name -> (y pitch / x pitch, options, far start).  On the oracle's
+# H at pts0 of r2_tan_adj_robust, h s^2 is 0.23 .. 0.61 in x and y and 5e-4 .. 0.04 in z: min_lm_diagonal = 0.9 clips all three of
+# every point, max_lm_diagonal = 0.5 x and y of the points above it.  At the radius 1e4 the damping is 1e-4 of the Hessian, so each
+# clamp runs once more where it decides the step: two iterations from the radius 1 (the oracle's cost then stands 6e-3 .. 0.6
+# relative away from the one without min_lm_diagonal, and 1e-6 .. 0.2 without max_lm_diagonal on 24 of the 40 points)
+TWO_STEPS = dict(initial_radius=1.0, max_iterations=2)
+OFF_DEFAULTS = {
+    "aniso_125": (od.A, {}, False),
+    "loss_scale_02": (None, dict(loss_scale=0.2), False),
+    "lm_min_binds": (None, dict(min_lm_diagonal=0.9), False),
+    "lm_min_binds_two_steps": (None, dict(min_lm_diagonal=0.9, **TWO_STEPS), False),
+    "lm_max_binds": (None, dict(max_lm_diagonal=0.5), False),
+    "lm_max_binds_two_steps": (None, dict(max_lm_diagonal=0.5, **TWO_STEPS), False),
+    "min_relative_decrease_09": (None, dict(min_relative_decrease=0.9), True),
+    "initial_radius_small": (None, dict(initial_radius=1e-2), False),
+}
+
+
+def oracle_points(sc, options, pts0=None):
+    """the oracle's one-point solves of all 40 points with `options`"""
+    start = np.asarray(sc.pts0 if pts0 is None else pts0).reshape(-1, 3)
+    oracle.set_fixed_frames(np.ones(len(sc.views_gt.reshape(-1)) // 6, np.uint8))
+    try:
+        return [oracle.solve(one_point_problem(sc, k, None, start[k]), options) for k in range(40)]
+    finally:
+        oracle.set_fixed_frames(None)
+
+
+@pytest.mark.parametrize("name", list(OFF_DEFAULTS))
+def test_points_follow_the_oracle_away_from_the_default_scalars_and_options(built, name):
+    a, kw, far = OFF_DEFAULTS[name]
+    key = FAMILIES[0][0]
+    sc = scene_of(key) if a is None else anisotropic_scene(scene_of(key), a)
+    o = od.options(**kw)
+    pts0 = np.asarray(sc.pts_gt).reshape(-1, 3) + np.array([0.0, 0.0, 20000.0]) if far else None
+    res = intersect(sc, options=o, pts0=pts0)
+    sums = [check_point(sc, k, res, options=o, pts0=pts0) for k in range(40)]
+    print_ranges()
+    # the oracle's side of the case: what the scalar or option changed against the defaults
+    if name == "aniso_125":
+        iso = batch(key)   # the y errors are in pixels of another pitch (and weigh 1 / a^2 in the cost: not the same minimiser)
+        assert np.median(np.abs(res.rms_y - iso.rms_y)) > 1e-3 and np.median(np.abs(res.rms_y - iso.rms_y)) > 10 * np.median(np.abs(res.rms_x - iso.rms_x))
+    elif name == "min_relative_decrease_09":
+        base = oracle_points(sc, od.options(), pts0)
+        assert all(s.unsuccessful_steps > 0 for s in sums)
+        assert sum(od.tuple_of(s) != od.tuple_of(b) for s, b in zip(sums, base)) >= 3   # and the option decided some of them
+    elif name == "initial_radius_small":
+        assert all(s.iterations >= b.iterations + 5 for s, b in zip(sums, oracle_points(sc, od.options())))
+    elif name == "loss_scale_02":
+        assert all(s.final_cost < b.final_cost for s, b in zip(sums, oracle_points(sc, od.options())))
+    elif "two_steps" in name:
+        d = np.array([abs(s.final_cost - b.final_cost) / b.final_cost for s, b in zip(sums, oracle_points(sc, od.options(**TWO_STEPS)))])
+        assert np.sum(d > 1e-6) >= (40 if "min" in name else 20)
 
 
 def test_more_observations_than_one_pass_of_the_wave(built):

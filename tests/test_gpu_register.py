@@ -29,7 +29,8 @@ import pytest
 import oracle
 from lifcal_amd import BundleAdjustment, _capi as capi, registerScene, scene
 from tests import register_reference as rr
-from tests.helpers import S
+from tests import off_defaults as od
+from tests.helpers import S, anisotropic_scene, spy_of
 
 pytestmark = pytest.mark.gpu
 
@@ -146,14 +147,14 @@ def one_frame(sc, got, f, obs=None):
     u, v, mcx, mcy, pt, fr = obs_of(sc) if obs is None else obs
     m = (fr == f) & got.mapped[pt]
     return capi.ProblemArrays(u[m], v[m], mcx[m], mcy[m], pt[m], np.zeros(int(m.sum()), np.uint32), sc.cam_gt, got.views[f].copy(), np.nan_to_num(got.pts).reshape(-1),
-                              sc.spx, sc.scale, (sc.config & rr.MODEL_BITS) | 0x100, fixed_mask=0x1FFFF)
+                              sc.spx, sc.scale, (sc.config & rr.MODEL_BITS) | 0x100, spy=spy_of(sc), fixed_mask=0x1FFFF)
 
 
 def one_point(sc, got, k, obs=None):
     u, v, mcx, mcy, pt, fr = obs_of(sc) if obs is None else obs
     m = (pt == k) & got.registered[fr]
     return capi.ProblemArrays(u[m], v[m], mcx[m], mcy[m], np.zeros(int(m.sum()), np.uint32), fr[m], sc.cam_gt, np.nan_to_num(got.views).reshape(-1), got.pts[k].copy(),
-                              sc.spx, sc.scale, (sc.config & rr.MODEL_BITS) | 0x500, fixed_mask=0x1FFFF)
+                              sc.spx, sc.scale, (sc.config & rr.MODEL_BITS) | 0x500, spy=spy_of(sc), fixed_mask=0x1FFFF)
 
 
 def check_stats(row, pa):
@@ -198,6 +199,31 @@ def check_rows(sc, got, point_costs=False, obs=None):
 def test_rows_against_the_oracle(built, key):
     check_rows(scene_of(key), device_default(key))
     print(f"{key}: rows within {max(MEASURED['rows']):.1e} px, final costs within {max(MEASURED['cost']):.1e} relative")
+
+
+def test_a_scene_with_a_y_pitch_of_its_own_is_registered_like_the_drivers(built):
+    """spy = 1.25 spx (tests/helpers.anisotropic_scene) through the whole chain, the bars of `driver` and `rows`; the driver with
+    spy = spx, which is what a pitch read from the x slot computes, ends millimetres away"""
+    key = "r1_tan_adj_robust"
+    spec, ms = CASES[key]
+    sc = anisotropic_scene(scene_of(key), od.A)
+    got = registerScene(sc.cam_gt, *obs_of(sc), spec.n_frames, spec.n_points, sc.config, sc.spx, sc.scale, spy=sc.spy, minShared=ms)
+    ref = rr.register("gpu", sc.cam_gt, *obs_of(sc), spec.n_frames, spec.n_points, sc.config, sc.spx, sc.scale, min_shared=ms, spy=sc.spy)
+    iso = rr.register("gpu", sc.cam_gt, *obs_of(sc), spec.n_frames, spec.n_points, sc.config, sc.spx, sc.scale, min_shared=ms)
+    assert_same_bookkeeping(got, ref)
+    reg, mp = ref.registered, ref.mapped
+    assert reg.sum() == spec.n_frames and mp.sum() >= 30
+    da = np.abs(got.views[reg, :3] - ref.views[reg, :3]).max()
+    dt = np.abs(got.views[reg, 3:] - ref.views[reg, 3:]).max() / np.abs(ref.views[reg, 3:]).max()
+    dp = (np.linalg.norm(got.pts[mp] - ref.pts[mp], axis=1) / np.linalg.norm(ref.pts[mp], axis=1)).max()
+    both = mp & iso.mapped
+    wrong = np.median(np.linalg.norm(iso.pts[both] - ref.pts[both], axis=1) / np.linalg.norm(ref.pts[both], axis=1))
+    print(f"anisotropic {key}: {ref.n_rounds} rounds, {int(mp.sum())} points; {da:.1e} rad, t {dt:.1e} and P {dp:.1e} relative; the driver with spy = spx: P {wrong:.1e} relative")
+    assert da <= 1e-6 and dt <= 1e-6 and dp <= 1e-6
+    assert wrong > 1e-3
+    assert [(int(got.frame_rows["iterations"][f]), int(got.frame_rows["termination"][f])) for f in np.flatnonzero(reg)] == [ref.f_last[int(f)][1:] for f in np.flatnonzero(reg)]
+    assert [(int(got.point_rows["iterations"][k]), int(got.point_rows["termination"][k])) for k in np.flatnonzero(mp)] == [ref.p_last[int(k)][1:] for k in np.flatnonzero(mp)]
+    check_rows(sc, got)
 
 
 def test_min_shared_not_reached_leaves_the_anchor_alone(built):

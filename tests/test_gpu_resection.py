@@ -16,7 +16,8 @@ import pytest
 
 import oracle
 from lifcal_amd import BundleAdjustment, _capi as capi, resectFrames, scene
-from tests.helpers import S, scaled_max_err, vec_err
+from tests import off_defaults as od
+from tests.helpers import S, anisotropic_scene, spy_of, scaled_max_err, vec_err
 
 pytestmark = pytest.mark.gpu
 
@@ -29,11 +30,15 @@ FAMILIES = [
 ]
 REJECTS = S(6, 40, None, 0x306, 115, outlier_fraction=0.05, init_rot_deg=25.0, init_trans_mm=100.0)
 LONG = S(3, 150, None, 0x306, 21, outlier_fraction=0.05)
+# starts from which some accepted steps of the defaults gain less than 0.9 of what the model promises (the oracle, defaults against
+# min_relative_decrease = 0.9: frame 1 of the first (10, 9, 0, 1) -> (13, 9, 3, 1), frame 4 of the second (9, 8, 0, 1) -> (17, 11, 5, 1); the other frames unchanged)
+REJECTS_FAR = S(6, 40, None, 0x306, 115, outlier_fraction=0.05, init_rot_deg=25.0, init_trans_mm=500.0)
+REJECTS_117 = S(6, 40, None, 0x306, 117, outlier_fraction=0.05, init_rot_deg=35.0, init_trans_mm=100.0)
 
 
 @functools.lru_cache(maxsize=None)
 def scene_of(key):
-    return scene.make_scene(dict(FAMILIES + [("rejects", REJECTS), ("long", LONG)])[key])
+    return scene.make_scene(dict(FAMILIES + [("rejects", REJECTS), ("rejects_far", REJECTS_FAR), ("rejects_117", REJECTS_117), ("long", LONG)])[key])
 
 
 def resect(sc, keep=None, options=None, order=None, views0=None, fr=None, n_frames=None):
@@ -46,13 +51,13 @@ def resect(sc, keep=None, options=None, order=None, views0=None, fr=None, n_fram
     v0 = sc.views0 if views0 is None else views0
     assert n_frames is None or len(v0) == 6 * n_frames
     return resectFrames(sc.cam_gt, sc.pts_gt, sc.u[idx], sc.v[idx], sc.mcx[idx], sc.mcy[idx], sc.pt[idx], frames, v0, sc.config, sc.spx, sc.scale,
-                        options=options)
+                        spy=spy_of(sc), options=options)
 
 
 def one_frame_problem(sc, f, keep, view):
     m = (sc.fr == f) if keep is None else ((sc.fr == f) & keep)
     return capi.ProblemArrays(sc.u[m], sc.v[m], sc.mcx[m], sc.mcy[m], sc.pt[m], np.zeros(int(m.sum()), np.uint32), sc.cam_gt, view, sc.pts_gt,
-                              sc.spx, sc.scale, sc.config, fixed_mask=0x1FFFF)
+                              sc.spx, sc.scale, sc.config, spy=spy_of(sc), fixed_mask=0x1FFFF)
 
 
 def check_frame(sc, f, res, keep=None, options=None):
@@ -74,6 +79,8 @@ def check_frame(sc, f, res, keep=None, options=None):
     assert abs(row["final_radius"] - s.final_radius) <= 1e-6 * s.final_radius
     # H, g: the oracle's sweep at the point where the kernel evaluated them, the resected pose
     o = capi.default_options_py(); o.jacobi_scaling = 0; o.min_lm_diagonal = 1e-300
+    if options is not None:
+        o.loss_scale = options.loss_scale
     sw = oracle.sweep(one_frame_problem(sc, f, keep, res.views[f]), radius=1e30, options=o)
     H_ref, g_ref = sw.S[17:23, 17:23], sw.gradient_reduced[17:23]
     # g at a (near) minimiser: its entries are what is left of sums that cancel by five to seven orders of magnitude, so the error of
@@ -111,6 +118,49 @@ def test_rejected_steps_walk_the_decrease_factor_path(built):
     assert (sums[1].iterations, sums[1].successful_steps, sums[1].unsuccessful_steps) == (14, 9, 4)   # the case is the one the bars were set on
     assert all(s.unsuccessful_steps == 0 and 6 <= s.iterations <= 7 for k, s in enumerate(sums) if k != 1)
     assert int(res.rows["unsuccessful_steps"][1]) == 4
+
+
+# away from the default scalars and options (tests/off_defaults.py): name -> (scene, y pitch / x pitch, options).  On the oracle's H at
+# the start poses of r2_tan_robust, h s^2 of the three rotations is 0.92 .. 0.999 and of the three translations 0 .. 0.17, so
+# max_lm_diagonal = 0.5 clips the former and min_lm_diagonal = 0.9 the latter, in every frame.  At the radius 1e4 the damping is
+# 1e-4 of the Hessian and LM corrects what is left of a wrong one, so each clamp runs once more where it decides the step: two
+# iterations from the radius 1, after which the oracle's cost stands 3e-4 .. 0.6 (relative) away from the one without the clamp
+TWO_STEPS = dict(initial_radius=1.0, max_iterations=2)
+OFF_DEFAULTS = {
+    "aniso_125": ("r2_tan_robust", od.A, {}),
+    "loss_scale_02": ("r2_tan_robust", None, dict(loss_scale=0.2)),
+    "lm_min_binds": ("r2_tan_robust", None, dict(min_lm_diagonal=0.9)),
+    "lm_min_binds_two_steps": ("r2_tan_robust", None, dict(min_lm_diagonal=0.9, **TWO_STEPS)),
+    "lm_max_binds": ("r2_tan_robust", None, dict(max_lm_diagonal=0.5)),
+    "lm_max_binds_two_steps": ("r2_tan_robust", None, dict(max_lm_diagonal=0.5, **TWO_STEPS)),
+    "min_relative_decrease_09": ("rejects_far", None, dict(min_relative_decrease=0.9)),
+    "min_relative_decrease_09_other_scene": ("rejects_117", None, dict(min_relative_decrease=0.9)),
+    "initial_radius_small": ("r2_tan_robust", None, dict(initial_radius=1e-2)),
+}
+
+
+@pytest.mark.parametrize("name", list(OFF_DEFAULTS))
+def test_frames_follow_the_oracle_away_from_the_default_scalars_and_options(built, name):
+    key, a, kw = OFF_DEFAULTS[name]
+    sc = scene_of(key) if a is None else anisotropic_scene(scene_of(key), a)
+    o = od.options(**kw)
+    res = resect(sc, options=o)
+    sums = [check_frame(sc, f, res, options=o) for f in range(6)]
+    # the oracle's side of the case: what the scalar or option changed against the defaults
+    defaults = lambda **kw: [oracle.solve(one_frame_problem(sc, f, None, sc.views0[6 * f: 6 * f + 6]), od.options(**kw)) for f in range(6)]
+    if name == "aniso_125":
+        iso = batch(key)   # the y errors are in pixels of another pitch (and weigh 1 / a^2 in the cost: not the same minimiser)
+        assert np.min(np.abs(res.rms_y - iso.rms_y)) > 1e-3 and np.min(np.abs(res.rms_y - iso.rms_y)) > 10 * np.min(np.abs(res.rms_x - iso.rms_x))
+    elif name.startswith("min_relative_decrease_09"):   # the option decides: steps the defaults accept are rejected
+        moved = [(od.tuple_of(s), od.tuple_of(b)) for s, b in zip(sums, defaults()) if od.tuple_of(s) != od.tuple_of(b)]
+        print(f"{name}: (iterations, accepted, rejected, termination) with the option against the defaults: {moved}")
+        assert moved and all(s[2] >= b[2] + 2 for s, b in moved)
+    elif name == "initial_radius_small":
+        assert all(s.iterations >= b.iterations + 5 for s, b in zip(sums, defaults()))
+    elif name == "loss_scale_02":
+        assert all(s.final_cost < 0.7 * b.final_cost for s, b in zip(sums, defaults()))
+    elif "two_steps" in name:   # the cost after two steps is not the one with 1e-6 / 1e32, by a thousand times its bar at least
+        assert all(abs(s.final_cost - b.final_cost) > 1e-5 * b.final_cost for s, b in zip(sums, defaults(**TWO_STEPS)))
 
 
 def test_more_observations_than_one_pass_of_the_workgroup(built):

@@ -29,7 +29,8 @@ import pytest
 import oracle
 from lifcal_amd import BundleAdjustment, _capi as capi, intersectPoints, resectFrames, scene, startPoints, startPoses
 from tests import start_reference as sr
-from tests.helpers import S
+from tests import off_defaults as od
+from tests.helpers import S, anisotropic_scene, spy_of
 
 pytestmark = pytest.mark.gpu
 
@@ -72,19 +73,22 @@ class Obs:
 
     def poses(self, gate=1.0):
         sc = self.sc
-        return startPoses(sc.cam_gt, self.pts, self.u, self.v, self.mcx, self.mcy, self.pt, self.fr, self.n_frames, sc.config, sc.spx, sc.scale, gatePx=gate, wantGroups=True)
+        return startPoses(sc.cam_gt, self.pts, self.u, self.v, self.mcx, self.mcy, self.pt, self.fr, self.n_frames, sc.config, sc.spx, sc.scale, spy=spy_of(sc),
+                          gatePx=gate, wantGroups=True)
 
     def points(self):
         sc = self.sc
-        return startPoints(sc.cam_gt, self.views, self.u, self.v, self.mcx, self.mcy, self.pt, self.fr, self.n_points, sc.config, sc.spx, sc.scale)
+        return startPoints(sc.cam_gt, self.views, self.u, self.v, self.mcx, self.mcy, self.pt, self.fr, self.n_points, sc.config, sc.spx, sc.scale,
+                           spy=spy_of(sc))
 
     def ref_groups(self, gate=1.0):
         sc = self.sc
-        return sr.group_rows(sc.cam_gt, self.u, self.v, self.mcx, self.mcy, self.pt, self.fr, sc.config, sc.spx, sc.scale, gate_px=gate)
+        return sr.group_rows(sc.cam_gt, self.u, self.v, self.mcx, self.mcy, self.pt, self.fr, sc.config, sc.spx, sc.scale, spy=spy_of(sc), gate_px=gate)
 
     def ref_points(self):
         sc = self.sc
-        return sr.start_points(sc.cam_gt, self.views, self.u, self.v, self.mcx, self.mcy, self.pt, self.fr, self.n_points, sc.config, sc.spx, sc.scale)
+        return sr.start_points(sc.cam_gt, self.views, self.u, self.v, self.mcx, self.mcy, self.pt, self.fr, self.n_points, sc.config, sc.spx, sc.scale,
+                               spy=spy_of(sc))
 
 
 @functools.lru_cache(maxsize=None)
@@ -160,7 +164,7 @@ def check_pose_rows(o, res, nan_frames=()):
             continue
         m = o.fr == f
         pa = capi.ProblemArrays(o.u[m], o.v[m], o.mcx[m], o.mcy[m], o.pt[m], np.zeros(int(m.sum()), np.uint32), sc.cam_gt, res.views[f].copy(), o.pts.reshape(-1),
-                                sc.spx, sc.scale, sc.config, fixed_mask=0x1FFFF)
+                                sc.spx, sc.scale, sc.config, spy=spy_of(sc), fixed_mask=0x1FFFF)
         check_stats(res.rows[f], res.rms_x[f], res.rms_y[f], pa)
     bad = res.status != 0
     assert not res.rows["sum_xx"][bad].any() and not res.rows["n_inliers"][bad].any() and np.all(np.isnan(res.rms_x[bad]))
@@ -188,7 +192,7 @@ def check_points(o, res, only=None):
         for k in (ok if only is None else only):
             m = o.pt == k
             pa = capi.ProblemArrays(o.u[m], o.v[m], o.mcx[m], o.mcy[m], np.zeros(int(m.sum()), np.uint32), o.fr[m], sc.cam_gt, o.views.reshape(-1), res.pts[k].copy(),
-                                    sc.spx, sc.scale, sc.config | 0x500, fixed_mask=0x1FFFF)
+                                    sc.spx, sc.scale, sc.config | 0x500, spy=spy_of(sc), fixed_mask=0x1FFFF)
             check_stats(res.rows[k], res.rms_x[k], res.rms_y[k], pa)
     finally:
         oracle.set_fixed_frames(None)
@@ -214,6 +218,32 @@ def test_points_of_the_families(built, key):
     o, _, res = batch(key)
     assert np.all(res.status == 0)
     check_points(o, res)
+    print_measured()
+
+
+def test_poses_and_points_with_a_y_pitch_of_its_own(built):
+    """spy = 1.25 spx (tests/helpers.anisotropic_scene) against the restatement with spy passed, on the families that have tangential
+    terms and centre adjustment; the restatement without spy, which is what a pitch read from the x slot computes, lies millimetres
+    away from it (4 .. 44 mm in the translations, metres in the points), where the bars are 1e-8 mm and 16 eps cond |P|"""
+    for key in ("r2_tan_robust", "r1_tan_adj_robust"):
+        o = Obs(anisotropic_scene(scene_of(key), od.A))
+        sc = o.sc
+        assert sc.spy == od.A * sc.spx
+        res, pres = o.poses(), o.points()
+        assert np.all(res.status == 0) and np.all(pres.status == 0)
+        check_groups(o, res)
+        check_poses(o, res)
+        check_pose_rows(o, res)
+        ref = check_points(o, pres)
+        obs = (o.u, o.v, o.mcx, o.mcy, o.pt, o.fr)
+        with_spy = sr.start_poses(sc.cam_gt, o.pts, *obs, o.n_frames, sc.config, sc.spx, sc.scale, spy=sc.spy)
+        iso_poses = sr.start_poses(sc.cam_gt, o.pts, *obs, o.n_frames, sc.config, sc.spx, sc.scale)
+        iso_points = sr.start_points(sc.cam_gt, o.views, *obs, o.n_points, sc.config, sc.spx, sc.scale)
+        dv, dp = np.max(np.abs(with_spy.views - iso_poses.views), axis=1), np.max(np.abs(ref.pts - iso_points.pts), axis=1)
+        print(f"{key}: restatement with spy = spx: poses {dv.min():.2e} .. {dv.max():.2e}, points {dp.min():.2e} .. {dp.max():.2e} mm away; "
+              f"GPU poses {np.max(np.abs(res.views - with_spy.views)):.1e} from the restatement's")
+        assert np.all(dv > 1e-2) and np.median(dp) > 1e-2
+        assert np.max(np.abs(res.views - with_spy.views)) <= 1e-6   # (the whole chain; check_poses holds the alignment to 1e-11 / 1e-8)
     print_measured()
 
 

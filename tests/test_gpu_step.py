@@ -8,20 +8,23 @@ Per case: create, sweep(radius, want_matrices), debug_step, at the radii 1e4 (th
   (b) the solver alone: row-wise backward error of delta_B on the GPU's own (S, rhs) against numpy.linalg.solve on the same system
   (c) the whole step: eta_B / eta_P of (delta_B, delta_P) on the matrix-free normal equations against the CPU reference step
   (d) gtd, ddd, step2, x2 against the same sums in long double from the returned delta, gradients and LM diagonal
+  (e) on the cases away from the default scalars and options: the returned LM diagonal against clip(h s^2, min, max) / (radius s^2)
+      of the reference, entry by entry, so that a clamp that binds is tested by its formula and not through the step
 The margin of 32 over the reference in (b) and (c) is reasoned, not measured: the reference and the kernels eliminate in different
 orders (LAPACK's pivoted LU; the chain, the two-ended chain, the odd-even reduction), the row-wise backward error is not bounded
 by Cholesky's analysis and scatters between two correct solvers (LU and Cholesky on the oracle's systems differ by up to 8x).
 """
 import dataclasses
-from typing import Optional
+from typing import Callable, Optional
 
 import numpy as np
 import pytest
 
 import oracle
 from lifcal_amd import BundleAdjustment, LifcalError, _capi as capi, scene
-from tests import step_reference as sr
-from tests.helpers import S, problem
+from lifcal_amd.bundle_adjustment import plan_stats
+from tests import off_defaults as od, step_reference as sr
+from tests.helpers import S, anisotropic, problem
 
 pytestmark = pytest.mark.gpu
 
@@ -30,6 +33,7 @@ RADII = (1e4, 7.0)
 LD = np.longdouble
 GLOBAL_CHAIN, LDS_CHAIN, TWISTED, ODD_EVEN = 0, 1, 2, 3
 ROUTE_ENV = ("LIFCAL_CR", "LIFCAL_TWISTED", "LIFCAL_DISABLE_BANDW")
+SWEEP_ENV = ("LIFCAL_SWEEP_KERNEL", "LIFCAL_DISABLE_V2", "LIFCAL_SWEEP_WAVES")
 
 
 @dataclasses.dataclass
@@ -43,6 +47,8 @@ class Case:
     whole_step: bool = True        # (c); off where the Jacobian is evaluated in fp32
     panel_in_lds: bool = True
     radii: tuple = RADII
+    transform: Optional[Callable] = None   # scene -> ProblemArrays in place of helpers.problem
+    lambdas: Optional[float] = None   # (e): its bar
 
 
 W24 = dict(outlier_fraction=0.02)
@@ -78,6 +84,37 @@ CASES = [
 # six frames: bw = 5, NA = 3 Q + 9, so Q >= 438 promoted points, which 652 constraints among 800 points give (650: Q = 436, 1348 rows)
 GLOBAL_PANEL = Case("global_panel_in_global_memory", S(6, 800, None, 0x506, 6210, n_constraints=652), GLOBAL_CHAIN, panel_in_lds=False, radii=(1e4,))
 
+
+# ---- away from the default scalars and options (tests/off_defaults.py; tests/test_off_defaults_cpu.py holds the conditions) --------------
+# spy = 1.25 spx, scale 1 and 3, other loss scales, LM-diagonal clamps that bind; all of them with (e), at 1e-12 where the Jacobian is fp64
+ANISO = lambda sc: anisotropic(sc, od.A)
+E = dict(lambdas=1e-12)
+ADJ_ROBUST_CONSTRAINTS = S(6, 40, None, 0xF06, 118, n_constraints=4, outlier_fraction=0.03)
+CLAMP_CASES = [Case(name, od.BASE, LDS_CHAIN, options=kw, **E) for name, (kw, _) in od.CLAMPS.items()]
+ANISO_125 = Case("aniso_125", od.BASE, LDS_CHAIN, transform=ANISO, **E)
+OFF_DEFAULT_CASES = [
+    ANISO_125,
+    Case("aniso_125_adj_robust_constraints", ADJ_ROBUST_CONSTRAINTS, LDS_CHAIN, transform=ANISO, **E),
+    # (e) of the fp32 evaluator: h is a sum of squares of Jacobian entries rounded to float32, not a sum that agrees to 1e-10 with the
+    # reference's.  An entry carries a few roundings of 2^-24 = 6e-8, its square twice that, and the sum of squares no more than its
+    # worst term: 16 roundings, 1e-6, is the bar (measured on an MI355X: 1.1e-7 on the reduced rows, 1.8e-7 on the points, three
+    # roundings; the fp64 arms measure 3e-16 .. 2e-14)
+    Case("aniso_125_precision1", od.BASE, LDS_CHAIN, options={"precision": 1}, whole_step=False, transform=ANISO, lambdas=16 * 2.0 ** -24),
+    Case("aniso_125_deterministic", od.BASE, LDS_CHAIN, options={"deterministic": 1}, transform=ANISO, **E),
+    Case("scale_1", od.SCALE_1, LDS_CHAIN, **E),
+    Case("scale_3", od.SCALE_3, LDS_CHAIN, **E),
+    Case("scale_3_aniso_125", od.SCALE_3, LDS_CHAIN, transform=ANISO, **E),
+] + [Case(name, od.ROBUST, LDS_CHAIN, options={"loss_scale": ls}, **E) for name, ls in od.LOSS_SCALES.items()] + CLAMP_CASES
+# the clamp cases and aniso_125 once more per damping site of the full sweep: k_sweep2, k_front4 + k_back4, the global-atomic kernels
+# with k_schur, and k_sweep3 with two waves per role (all fp64 and unordered: no pairing here that create() refuses or redirects)
+SWEEP_SETTINGS = [{"LIFCAL_SWEEP_KERNEL": "2"}, {"LIFCAL_SWEEP_KERNEL": "4"}, {"LIFCAL_DISABLE_V2": "1"}, {"LIFCAL_SWEEP_WAVES": "2"}]
+# lanes per pass of the plan create() makes in each of them (lifcal_ba_plan_stats: 64 is k_front4 + k_back4, 128 k_sweep3 with two
+# waves per role, 256 k_sweep3 and k_sweep2), so that a fallback to k_sweep3 cannot take a case's damping site away unnoticed
+PASS_LANES = {"LIFCAL_SWEEP_KERNEL": {"2": 256, "4": 64}, "LIFCAL_SWEEP_WAVES": {"2": 128}}
+OFF_DEFAULT_CASES += [dataclasses.replace(c, id=c.id + "_" + "_".join(f"{k[7:].lower()}_{v}" for k, v in env.items()), env=env)
+                      for env in SWEEP_SETTINGS for c in CLAMP_CASES + [ANISO_125]]
+
+
 def make_options(case):
     o = capi.default_options_py()
     for k, v in case.options.items():
@@ -86,7 +123,7 @@ def make_options(case):
 
 
 def set_route_env(monkeypatch, env):
-    for k in ROUTE_ENV:
+    for k in ROUTE_ENV + SWEEP_ENV:
         monkeypatch.delenv(k, raising=False)
     for k, v in env.items():
         monkeypatch.setenv(k, v)
@@ -125,7 +162,7 @@ def step_scalars_reference(pa, ne, sw, st, frame_live):
     return dict(gtd=gtd, ddd=ddd, step2=step2, x2=x2)
 
 
-def candidate_cost(pa, ne, st):
+def candidate_cost(pa, ne, st, loss_scale=0.5):
     """the oracle's cost at x + delta (camera through the box projection, as the kernels apply it)"""
     sc_pa = capi.ProblemArrays(pa.u, pa.v, pa.mcx, pa.mcy, pa.pt, pa.fr, pa.cam, pa.views, pa.pts, pa.struct.spx, pa.struct.scale, pa.struct.config,
                                spy=pa.struct.spy, fixed_mask=pa.struct.fixed_mask, lower=pa.lower, upper=pa.upper, c_i=pa.c_i, c_j=pa.c_j,
@@ -138,19 +175,20 @@ def candidate_cost(pa, ne, st):
     sc_pa.cam[:] = cam
     sc_pa.views[:] = pa.views + st.delta_reduced[17:ne.nb]
     sc_pa.pts[:] = pa.pts + st.delta_points
-    return oracle.cost(sc_pa, threads=4)
+    return oracle.cost(sc_pa, loss_scale=loss_scale, threads=4)
 
 
 def check_case(case, monkeypatch):
     set_route_env(monkeypatch, case.env)
     sc = scene.make_scene(case.spec)
-    pa = problem(sc)
+    pa = problem(sc) if case.transform is None else case.transform(sc)
     o = make_options(case)
     F = case.spec.n_frames
     fixed = None
     if case.fixed_frames is not None:
         fixed = np.zeros(F, np.uint8); fixed[list(case.fixed_frames)] = 1
-    ne = sr.NormalEquations(pa, RADII[0], jacobi_scaling=bool(o.jacobi_scaling), fixed_frames=fixed)
+    ne = sr.NormalEquations(pa, RADII[0], jacobi_scaling=bool(o.jacobi_scaling), fixed_frames=fixed, loss_scale=o.loss_scale,
+                            lm_min=o.min_lm_diagonal, lm_max=o.max_lm_diagonal)
     n_dead = ne.check_dead_rows()
     frame_live = np.zeros(F, bool); frame_live[np.unique(pa.fr)] = True
     if fixed is not None:
@@ -164,13 +202,22 @@ def check_case(case, monkeypatch):
     with BundleAdjustment(pa, o) as ba:
         if fixed is not None:
             ba.set_fixed_frames(fixed)
+        info = ba.info()
+        for k, v in case.env.items():
+            if k == "LIFCAL_DISABLE_V2":
+                assert info.n_chunks == 0 and info.n_tiles > 0, (info.n_chunks, info.n_tiles)   # every point through the global-atomic kernels
+            elif k in PASS_LANES:
+                st = plan_stats(pa)
+                assert info.n_chunks == st.n_blocks > 0 and st.pass_lanes == PASS_LANES[k][v], (info.n_chunks, st.n_blocks, st.pass_lanes)
+                assert info.n_tiles == st.n_passes * (st.pass_lanes // 64), (info.n_tiles, st.n_passes)   # no point left to the other kernels
         for radius in case.radii:
             tag = f"[{case.id} r={radius:g}]"
             sw = ba.sweep(radius, want_matrices=True)
             st = ba.debug_step()
             n_red = sw.n_reduced
             # (a) the route
-            print(f"{tag} route {st.route} panel_in_lds {int(st.panel_in_lds)} n_reduced {n_red} n_full {ne.n} dead rows {n_dead} promoted {sw.n_promoted}")
+            print(f"{tag} route {st.route} panel_in_lds {int(st.panel_in_lds)} n_reduced {n_red} n_full {ne.n} dead rows {n_dead} promoted {sw.n_promoted}"
+                  f" | sweep {case.env or 'k_sweep3 (default)'}: {info.n_chunks} window blocks, {info.n_tiles} tiles")
             assert st.route == case.route and st.panel_in_lds == case.panel_in_lds, (st.route, st.panel_in_lds)
             assert sw.n_promoted == len(ne.promoted) and n_red == ne.nb + 3 * len(ne.promoted)
             # (b) the solver alone, on its own system
@@ -201,9 +248,22 @@ def check_case(case, monkeypatch):
                 tol = 8 * cnt * sr.EPS * mag
                 print(f"{tag} (d) {name} {got:.17g}  long double {val:.17g}  |diff| {abs(got - val):.3e}  tolerance {tol:.3e}")
                 expect(abs(got - val) <= tol, f"{tag} (d) {name}: {got!r} against {val!r}, tolerance {tol:.3e}")
+            # (e) the LM diagonal itself: clip(h s^2, min, max) / (radius s^2) of the reference on every live row.  Both sides are one
+            # fp64 multiply, clip and divide of sums h that agree to 1e-10 (the sweep's bar), so 1e-12 is two orders above them
+            if case.lambdas is not None:
+                ne.set_radius(radius)
+                lam = ne.lam.astype(np.float64)
+                lam_B, live_B = ne.reduced(lam), ne.reduced(ne.live)
+                elim_rows = (ne.rows_P & ne.live)[ne.nb:]
+                below, above = od.clip_counts(ne, o.min_lm_diagonal, o.max_lm_diagonal)
+                eB = float(np.max(np.abs(st.lambda_reduced[live_B] - lam_B[live_B]) / lam_B[live_B]))
+                eP = float(np.max(np.abs(st.lambda_points[elim_rows] - lam[ne.nb:][elim_rows]) / lam[ne.nb:][elim_rows])) if np.any(elim_rows) else 0.0
+                print(f"{tag} (e) lambda: reduced {eB:.3e}  points {eP:.3e}  ({case.lambdas:g}); clipped from below {below}, from above {above} of {int(np.sum(ne.live))}")
+                expect(eB <= case.lambdas, f"{tag} (e) lambda_reduced off by {eB:.3e}")
+                expect(eP <= case.lambdas, f"{tag} (e) lambda_points off by {eP:.3e}")
             # the candidate's cost belongs to x + delta: two fp64 evaluations of the model summed in different orders (the suite holds
             # the sweep's cost to 1e-12 of the oracle's at these sizes; the candidate point is rebuilt here from delta in the same fp64 adds)
-            cc = candidate_cost(pa, ne, st)
+            cc = candidate_cost(pa, ne, st, o.loss_scale)
             print(f"{tag} cand_cost {st.cand_cost:.17g}  oracle at x + delta {cc:.17g}  relative {abs(st.cand_cost - cc) / cc:.3e}")
             expect(abs(st.cand_cost - cc) <= 1e-10 * cc, f"{tag} cand_cost {st.cand_cost!r} against {cc!r}")
     assert not failures, "\n".join(failures)
@@ -211,6 +271,11 @@ def check_case(case, monkeypatch):
 
 @pytest.mark.parametrize("case", CASES, ids=[c.id for c in CASES])
 def test_step_solves_the_normal_equations(built, monkeypatch, case):
+    check_case(case, monkeypatch)
+
+
+@pytest.mark.parametrize("case", OFF_DEFAULT_CASES, ids=[c.id for c in OFF_DEFAULT_CASES])
+def test_step_away_from_the_default_scalars_and_options(built, monkeypatch, case):
     check_case(case, monkeypatch)
 
 
