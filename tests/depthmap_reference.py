@@ -152,7 +152,7 @@ def accuracy(name: str, scene: str, dm, scale: int) -> dict:
     """e = inv_depth - 1 / depth_fn(x_v, y_v) at the cell centres at least ceil(1.5 d / scale) from the border (on `step` without
     the band about STEP_X): inlier RMS, |median e|, measured and covered share, outlier share among the valued cells; on `step`
     also the share of cells inside the band that lie farther than OUTLIER from both planes, for status 0 and for status 1"""
-    d = ref.CASES[name][2]
+    d = ref.case(name)[2]
     status, iv = np.asarray(dm.status), np.asarray(dm.inv_depth)
     oh, ow = status.shape
     m = int(math.ceil(1.5 * d / scale))
@@ -202,6 +202,10 @@ MEASURED = {
     "d14": dict(rms=0.00207, median=0.00081),        # near scene with noise; far scene
     "d23_16": dict(rms=0.00081, median=0.00079),     # mid scene, both
     "d9_pitch": dict(rms=0.00243, median=0.00122),   # near scene with noise; far scene with noise
+    # rawdepth_reference.GEOMETRY_CASES, measured the same way (tests/test_depthmap_cpu.py runs both noise levels for them)
+    "d14_rot": dict(rms=0.00215, median=0.00040),        # near scene with noise, scale 1; near scene with noise, scale 2
+    "d17_sq": dict(rms=0.00158, median=0.00047),         # near scene with noise, scale 1; mid scene with noise, scale 2
+    "d14_rot_off": dict(rms=0.00201, median=0.00073),    # near scene with noise, scale 1; far scene with noise, scale 2
 }
 BARS = {name: dict(rms=2 * m["rms"], median=2 * m["median"]) for name, m in MEASURED.items()}
 

@@ -224,6 +224,35 @@ CASES = {
     "d9_pitch": (203, 131, 9.3, 0.0, (0.0, 0.0), 8, 1, 13),
 }
 BASE_Y = (-0.5, 0.8660254)
+# Grids beyond the lattice of CASES (BASE_Y, rotation on the grid and next to zero), for the tests of the whole image chain on other
+# geometries; a table of its own, so that the tests parametrised over CASES stay what they are.  The record of CASES and then
+# lens_base_y, rotation_on_grid.  d14_rot: d14 turned by 0.03 rad.  d17_sq: the squeezed lattice of tests/test_gpu_mla.py's
+# rotated_neg, whose six nearest neighbours are not equidistant (four at 0.995 d, two at d).  d14_rot_off: the rotation is not the
+# grid's (rotation_on_grid = 0), so the lenses lie on the UNROTATED lattice, and the image is rendered there.  (At 16 bit with patch
+# radius 2 the restatement does not meet CONDITIONS on 14.3-pixel lenses, coverage 0.04 near and 0.66 mid, so it is d14's 8 bit
+# with radius 1.)
+GEOMETRY_CASES = {
+    "d14_rot": (200, 160, 14.3, 0.03, (3.7, -5.4), 8, 1, 0, BASE_Y, True),
+    "d17_sq": (211, 157, 17.35, -0.021, (5.25, 7.5), 8, 1, 0, (0.5, 0.86), True),
+    "d14_rot_off": (200, 160, 14.3, 0.03, (0.7, -0.4), 8, 1, 0, BASE_Y, False),
+}
+# a grid of lenses so small that at patch radius 2 no pair counts (valid_r = 2.25: r0 = 0.25, r1 < 0), for the option tests
+OPTION_CASES = {"d6": (96, 80, 6.5, 0.0, (0.0, 0.0), 8, 1, 0, BASE_Y, True)}
+
+
+def case(name: str) -> tuple:
+    """the record of a case of any table, with lens_base_y and rotation_on_grid (BASE_Y and on the grid for CASES)"""
+    if name in CASES:
+        return CASES[name] + (BASE_Y, True)
+    return GEOMETRY_CASES[name] if name in GEOMETRY_CASES else OPTION_CASES[name]
+
+
+def grid_rotation(name: str) -> float:
+    """the rotation of the lattice the lenses lie on: the case's, or 0 where the rotation is not the grid's"""
+    c = case(name)
+    return c[3] if c[9] else 0.0
+
+
 STEP_X, STEP_EXCLUDE = 100.3, 12.0
 # The scenes: fronto-parallel planes at a near, a middle and a far virtual depth, and one depth step at x_v = STEP_X.
 # near / mid / far / (left, right of the step).  The 9.3-pixel lenses of d9_pitch cannot measure the depths of the other two
@@ -235,6 +264,8 @@ SCENE_DEPTHS = {
     "d23_16": dict(near=2.6, mid=4.0, far=7.0, step=(3.2, 5.5)),
     "d9_pitch": dict(near=4.5, mid=5.5, far=7.0, step=(5.0, 7.0)),
 }
+SCENE_DEPTHS.update({name: SCENE_DEPTHS["d14"] for name in GEOMETRY_CASES})
+SCENE_DEPTHS["d6"] = SCENE_DEPTHS["d9_pitch"]
 SCENE_NAMES = ("near", "mid", "far", "step")
 TEXTURE = dict(seed=7, lambda_min=18.0, lambda_max=60.0)   # at least 2.5 v raw pixels in the virtual image up to v = 7
 NOISE = 0.004
@@ -244,6 +275,7 @@ CONDITIONS = {"near": (0.30, 0.04), "mid": (0.70, 0.015), "far": (0.70, 0.015), 
 OUTLIER = 0.02
 # neighbour sets the accuracy is measured and tested with (max_baseline): d9_pitch's conditions need the 18
 ACCURACY_BASELINES = {"d14": (1.05, 2.1), "d23_16": (1.05, 2.1), "d9_pitch": (2.1,)}
+ACCURACY_BASELINES.update({name: (1.05, 2.1) for name in GEOMETRY_CASES})
 
 
 def scene_depth(name: str, scene: str):
@@ -259,8 +291,8 @@ def texture():
 @functools.lru_cache(maxsize=None)
 def make_case(name: str, scene: str, noise: float = 0.0) -> np.ndarray:
     """the rendered raw image of a case (cached: shared by the tests, never modified)"""
-    w, h, d, rot, off, bits, _, _ = CASES[name]
-    tx, ty = white_image.grid_centres(w, h, d, BASE_Y, rot, off, 1.5)
+    w, h, d, _, off, bits, _, _, base_y, _ = case(name)
+    tx, ty = white_image.grid_centres(w, h, d, base_y, grid_rotation(name), off, 1.5)
     img = raw_image.render_raw_image(w, h, tx, ty, d, scene_depth(name, scene), texture(), bits=bits, noise=noise, seed=11)
     img.setflags(write=False)
     return img
@@ -269,7 +301,7 @@ def make_case(name: str, scene: str, noise: float = 0.0) -> np.ndarray:
 def true_inverse_depth(name: str, scene: str, cx32, cy32, map_ml: np.ndarray) -> np.ndarray:
     """1 / v of what each pixel shows, through the centre of the lens the library assigns it to (NaN without a lens); also
     the virtual-image x of the pixel, which the step scene's exclusion band needs"""
-    w, h = CASES[name][0], CASES[name][1]
+    w, h = case(name)[:2]
     yy, xx = np.meshgrid(np.arange(h, dtype=np.float64), np.arange(w, dtype=np.float64), indexing="ij")
     lens = np.where(map_ml >= 0, map_ml, 0)
     lcx, lcy = np.asarray(cx32, np.float64)[lens], np.asarray(cy32, np.float64)[lens]
@@ -297,6 +329,10 @@ MEASURED = {
     "d14": dict(rms=0.00386, median=0.00076),        # near scene with noise; far scene with 18 neighbours
     "d23_16": dict(rms=0.00100, median=0.00076),     # step scene with noise; mid scene with 18 neighbours
     "d9_pitch": dict(rms=0.00446, median=0.00117),   # near scene with noise; far scene
+    # GEOMETRY_CASES, measured the same way (tests/test_rawdepth_cpu.py runs both noise levels for them)
+    "d14_rot": dict(rms=0.00410, median=0.00059),        # near scene with noise, 6 neighbours; near scene, 18 neighbours
+    "d17_sq": dict(rms=0.00303, median=0.00134),         # near scene with noise, 6 neighbours; far scene, 6 neighbours
+    "d14_rot_off": dict(rms=0.00375, median=0.00067),    # near scene with noise, 6 neighbours; far scene, 6 neighbours
 }
 BARS = {name: dict(rms=2 * m["rms"], median=2 * m["median"]) for name, m in MEASURED.items()}
 
@@ -313,26 +349,29 @@ class GridData:
 def grid_data(name: str, grid) -> GridData:
     """what the restatement needs of a micro-lens grid: `grid` has lenses() and maps() (lifcal_amd.MicroLensGrid on the GPU, or
     oracle.mla.MicroLensGrid, whose lists and maps are the same bits)"""
-    w, h, d, rot, off = CASES[name][:5]
+    w, h, d, rot, off, _, _, _, base_y, on_grid = case(name)
     cx, cy, _ = grid.lenses()
     map_ml, _ = grid.maps()
-    return GridData(cx, cy, map_ml, sub_grid_of(cx, cy, d, BASE_Y, rot, off, w, h))
+    return GridData(cx, cy, map_ml, sub_grid_of(cx, cy, d, base_y, rot, off, w, h, on_grid))
 
 
 def grid_arguments(name: str):
     """positional arguments of MicroLensGrid for a case"""
-    w, h, d, rot, off = CASES[name][:5]
-    return w, h, d, BASE_Y, rot, off
+    w, h, d, rot, off, _, _, _, base_y, on_grid = case(name)
+    return w, h, d, base_y, rot, off, on_grid
 
 
 _RUNS = {}
 
 
-def run(name: str, scene: str, noise: float, gd: GridData, **opts) -> Estimate:
-    """the restatement on a case's image (cached: computed once, shared by the tests, never modified)"""
-    key = (name, scene, noise, tuple(sorted(opts.items())))
+def run(name: str, scene: str, noise: float, gd: GridData, tables_rotation=None, **opts) -> Estimate:
+    """the restatement on a case's image (cached: computed once, shared by the tests, never modified).  patch_radius is the case's
+    unless given.  tables_rotation: build the tables for a lattice turned by this angle instead of the case's own, a deliberately
+    WRONG restatement for the tests that show which cases can tell."""
+    key = (name, scene, noise, tables_rotation, tuple(sorted(opts.items())))
     if key not in _RUNS:
-        w, h, d, rot, off, bits, pr, _ = CASES[name]
-        opt = options(bits, patch_radius=pr, **opts)
-        _RUNS[key] = estimate(make_case(name, scene, noise), gd.cx, gd.cy, gd.map_ml, gd.sub, tables(d, BASE_Y, rot, opt), opt)
+        w, h, d, rot, off, bits, pr, _, base_y, on_grid = case(name)
+        opt = options(bits, **{"patch_radius": pr, **opts})
+        tab = tables(d, base_y, rot, opt, on_grid) if tables_rotation is None else tables(d, base_y, tables_rotation, opt, True)
+        _RUNS[key] = estimate(make_case(name, scene, noise), gd.cx, gd.cy, gd.map_ml, gd.sub, tab, opt)
     return _RUNS[key]

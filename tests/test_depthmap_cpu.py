@@ -16,8 +16,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def params(name):
-    w, h, d, base_y, rot, off = ref.grid_arguments(name)
-    return capi.MlaParams(w, h, d, (C.c_float * 2)(*base_y), rot, (C.c_float * 2)(*off), 1)
+    w, h, d, base_y, rot, off, on_grid = ref.grid_arguments(name)
+    return capi.MlaParams(w, h, d, (C.c_float * 2)(*base_y), rot, (C.c_float * 2)(*off), 1 if on_grid else 0)
 
 
 def test_exports_and_layout(built):
@@ -156,3 +156,21 @@ def test_restatement_accuracy(built, name):
             assert np.array_equal(dm.depth16 > 0, valued)
             back = 1.0 - dm.depth16[valued].astype(np.float64) / 65535.0
             assert np.abs(back - dm.q[valued] / dref.Q).max() <= 0.5 / 65535 + 1e-12
+
+
+@pytest.mark.parametrize("name", list(ref.GEOMETRY_CASES))
+def test_restatement_accuracy_on_other_geometries(built, name):
+    """the twin of test_restatement_accuracy on the rotated, the squeezed and the rotation-off-grid lattice of
+    rawdepth_reference.GEOMETRY_CASES, at noise 0 and NOISE: this is where MEASURED of these cases is measured"""
+    from oracle.mla import MicroLensGrid
+    gd = ref.grid_data(name, MicroLensGrid(*ref.grid_arguments(name)))
+    for scn in ref.SCENE_NAMES:
+        for noise in (0.0, ref.NOISE):
+            for scale in dref.SCALES:
+                dm = dref.run(name, scn, noise, gd, scale)
+                a = dref.accuracy(name, scn, dm, scale)
+                print(f"{name} {scn} noise {noise} scale {scale}: {dref.describe(a)}; counts {dm.counts.tolist()}, {dm.n_samples} samples")
+                dref.check_conditions(scn, a)
+                assert a["rms"] <= dref.MEASURED[name]["rms"] and a["median"] <= dref.MEASURED[name]["median"], (scn, noise, scale, a)
+                assert int(dm.counts.sum()) == dm.status.size
+                assert np.array_equal(dm.depth16 > 0, dm.status <= 1)

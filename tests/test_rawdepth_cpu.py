@@ -15,8 +15,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def params(name):
-    w, h, d, base_y, rot, off = ref.grid_arguments(name)
-    return capi.MlaParams(w, h, d, (C.c_float * 2)(*base_y), rot, (C.c_float * 2)(*off), 1)
+    w, h, d, base_y, rot, off, on_grid = ref.grid_arguments(name)
+    return capi.MlaParams(w, h, d, (C.c_float * 2)(*base_y), rot, (C.c_float * 2)(*off), 1 if on_grid else 0)
 
 
 def test_exports_and_layout(built):
@@ -89,11 +89,22 @@ def test_argument_errors(built):
 @pytest.mark.parametrize("name", list(ref.CASES))
 def test_plan_matches_restatement_tables(built, name):
     """6 and 18 neighbours at the two baselines, the same for both sub-grids, and a window that holds every shift of the tables"""
-    w, h, d, rot, off, bits, pr, _ = ref.CASES[name]
+    check_plan(name)
+
+
+@pytest.mark.parametrize("name", list(ref.GEOMETRY_CASES))
+def test_plan_matches_restatement_tables_on_other_geometries(built, name):
+    """the same on the rotated, the squeezed and the rotation-off-grid lattice: 1.05 d still selects 6 and 2.1 d 18 where the six
+    nearest are not equidistant"""
+    check_plan(name)
+
+
+def check_plan(name):
+    w, h, d, rot, off, bits, pr, _, base_y, on_grid = ref.case(name)
     img = np.zeros((h, w), np.uint8 if bits == 8 else np.uint16)
     for mb, n in ((1.05, 6), (2.1, 18)):
         opt = ref.options(bits, patch_radius=pr, max_baseline=mb)
-        tab = ref.tables(d, ref.BASE_Y, rot, opt)
+        tab = ref.tables(d, base_y, rot, opt, on_grid)
         plan = raw_depth.checkRawDepth(params(name), img, patch_radius=pr, max_baseline=mb)
         assert plan.n_neighbours == n == len(tab.delta[0]) == len(tab.delta[1])
         # a neighbour of sub-grid 0 is minus a neighbour of sub-grid 1
@@ -120,6 +131,74 @@ def test_restatement_accuracy(built, name):
             assert a["coverage"] >= cov_min and a["outliers"] <= out_max, (scn, mb, a)
             assert a["rms"] <= ref.MEASURED[name]["rms"] and a["median"] <= ref.MEASURED[name]["median"], (scn, mb, a)
             assert int(est.counts.sum()) == est.status.size
+
+
+def oracle_grid(name):
+    from oracle.mla import MicroLensGrid
+    return ref.grid_data(name, MicroLensGrid(*ref.grid_arguments(name)))
+
+
+def lenses_lie_on_rendered_lattice(name, gd):
+    """the largest distance of a lens centre of the library from the nearest centre the image is rendered with (for d14_rot_off
+    that is the UNROTATED lattice)"""
+    w, h, d, _, off, _, _, _, base_y, _ = ref.case(name)
+    tx, ty = white_image.grid_centres(w, h, d, base_y, ref.grid_rotation(name), off, 1.5)
+    dist = np.hypot(gd.cx.astype(np.float64)[:, None] - tx[None, :], gd.cy.astype(np.float64)[:, None] - ty[None, :]).min(axis=1)
+    return float(dist.max())
+
+
+@pytest.mark.parametrize("name", list(ref.GEOMETRY_CASES))
+def test_restatement_accuracy_on_other_geometries(built, name):
+    """the twin of test_restatement_accuracy on the rotated, the squeezed and the rotation-off-grid lattice, at noise 0 and NOISE
+    and with 6 and 18 neighbours: this is where MEASURED of these cases is measured.  First the case is shown not to be vacuous:
+    the library's lenses lie where the image was rendered (on the unrotated lattice for d14_rot_off, whatever its rotation says)."""
+    gd = oracle_grid(name)
+    off_lattice = lenses_lie_on_rendered_lattice(name, gd)
+    print(f"{name}: {len(gd.cx)} lenses, at most {off_lattice:.2e} px from the rendered lattice, sub-grids {np.bincount(gd.sub).tolist()}")
+    assert off_lattice < 1e-3
+    for scn in ref.SCENE_NAMES:
+        cov_min, out_max = ref.CONDITIONS[scn]
+        for mb in ref.ACCURACY_BASELINES[name]:
+            for noise in (0.0, ref.NOISE):
+                est = ref.run(name, scn, noise, gd, max_baseline=mb)
+                a = ref.accuracy(name, scn, est, gd.cx, gd.cy, gd.map_ml)
+                print(f"{name} {scn} max_baseline {mb} noise {noise}: coverage {a['coverage']:.3f}, outliers {a['outliers']:.4f}, inlier rms {a['rms']:.5f}, "
+                      f"|median| {a['median']:.5f} over {a['n']} pixels; counts {est.counts.tolist()}")
+                assert a["coverage"] >= cov_min and a["outliers"] <= out_max, (scn, mb, noise, a)
+                assert a["rms"] <= ref.MEASURED[name]["rms"] and a["median"] <= ref.MEASURED[name]["median"], (scn, mb, noise, a)
+                assert int(est.counts.sum()) == est.status.size
+
+
+# name: the rotation the mutant's tables are built for (on the grid) instead of the case's own
+WRONG_ROTATION = {"d14": -0.003, "d14_rot": -0.03, "d17_sq": 0.021, "d14_rot_off": 0.03}
+
+
+@pytest.mark.parametrize("name", list(WRONG_ROTATION))
+def test_wrong_rotation_in_the_tables_is_seen_only_on_the_rotated_grids(built, name):
+    """a mutation check: the restatement with its tables built for the WRONG rotation (the sign flipped; for d14_rot_off the
+    rotation taken to be the grid's), mid scene at NOISE, against the conditions and bars of the accuracy tests.  The kernel's
+    tables and the restatement's are built the same way, so equal bytes cannot see such a mistake; only the true depth can.
+    On d14 (0.003 rad) the mutant passes every condition and bar at both neighbour sets: that is the gap the cases of CASES leave.
+    On d14_rot, d17_sq and d14_rot_off it fails the outlier cap with 18 neighbours, all three asserted (measured: outliers 0.248,
+    0.078, 0.036 against 0.015; with 6 neighbours 0.119, 0.029, 0.0095, the last within the cap, so 18 it is)."""
+    gd = oracle_grid(name)
+    cov_min, out_max = ref.CONDITIONS["mid"]
+    bars = ref.BARS[name]
+    passes = {}
+    for mb in (1.05, 2.1):
+        good = ref.accuracy(name, "mid", ref.run(name, "mid", ref.NOISE, gd, max_baseline=mb), gd.cx, gd.cy, gd.map_ml)
+        a = ref.accuracy(name, "mid", ref.run(name, "mid", ref.NOISE, gd, tables_rotation=WRONG_ROTATION[name], max_baseline=mb), gd.cx, gd.cy, gd.map_ml)
+        passes[mb] = a["coverage"] >= cov_min and a["outliers"] <= out_max and a["rms"] <= bars["rms"] and a["median"] <= bars["median"]
+        print(f"{name} max_baseline {mb} tables for rotation {WRONG_ROTATION[name]}: coverage {a['coverage']:.3f}, outliers {a['outliers']:.4f}, "
+              f"inlier rms {a['rms']:.5f} (bar {bars['rms']:.5f}), |median| {a['median']:.5f} (bar {bars['median']:.5f}): "
+              f"{'passes' if passes[mb] else 'FAILS'}; the right tables: outliers {good['outliers']:.4f}, inlier rms {good['rms']:.5f}")
+        assert good["coverage"] >= cov_min and good["outliers"] <= out_max and good["rms"] <= bars["rms"] and good["median"] <= bars["median"]
+        if mb == 2.1 and name != "d14":
+            assert a["outliers"] > out_max or a["rms"] > bars["rms"], (name, a, bars)
+    if name == "d14":
+        assert passes[1.05] and passes[2.1]          # the gap: a sign error of the rotation would pass the tests on CASES alone
+    else:
+        assert not passes[2.1]
 
 
 def test_renderer_geometry():

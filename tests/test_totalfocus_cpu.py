@@ -17,8 +17,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def params(name):
-    w, h, d, base_y, rot, off = ref.grid_arguments(name)
-    return capi.MlaParams(w, h, d, (C.c_float * 2)(*base_y), rot, (C.c_float * 2)(*off), 1)
+    w, h, d, base_y, rot, off, on_grid = ref.grid_arguments(name)
+    return capi.MlaParams(w, h, d, (C.c_float * 2)(*base_y), rot, (C.c_float * 2)(*off), 1 if on_grid else 0)
 
 
 def oracle_grid(name):
@@ -257,3 +257,27 @@ def test_restatement_uses_the_white_image(built, name):
         assert aw["share"] == 1.0 and aw["rms"] <= tref.MEASURED[name]["rms"], (scn, aw)
         tref.check_registration(aw, (name, scn))
         assert ap["rms"] > tref.BARS[name]["rms"], (scn, ap)
+
+
+@pytest.mark.parametrize("name", list(ref.GEOMETRY_CASES))
+def test_restatement_accuracy_on_other_geometries(built, name):
+    """the twin of the two accuracy tests above on the rotated, the squeezed and the rotation-off-grid lattice of
+    rawdepth_reference.GEOMETRY_CASES, with the true depth and with the depth map of the restatement chain, at noise 0 and NOISE:
+    this is where MEASURED of these cases is measured"""
+    gd = oracle_grid(name)
+    for scn in ref.SCENE_NAMES:
+        for noise in (0.0, ref.NOISE):
+            for scale in tref.SCALES:
+                tf = tref.run_true(name, scn, noise, gd, scale)
+                a = tref.accuracy(name, scn, tf, scale)
+                print(f"{name} {scn} noise {noise} scale {scale} true depth: {tref.describe(a)}; counts {tf.counts.tolist()}")
+                assert a["share"] == 1.0 and a["min_lenses"] >= 1, (scn, noise, scale, a)
+                tref.check_registration(a, (name, scn, noise, scale))
+                assert a["rms"] <= tref.MEASURED[name]["rms"], (scn, noise, scale, a)
+                tf, dm = tref.run_chained(name, scn, noise, gd, scale)
+                a = tref.accuracy(name, scn, tf, scale)
+                inner = tref.interior(name, scn, scale)
+                print(f"{name} {scn} noise {noise} scale {scale} chained depth: {tref.describe(a)}; counts {tf.counts.tolist()}")
+                assert np.array_equal(inner & (tf.status == 0), inner & (dm.status <= 1)), (scn, noise, scale)
+                tref.check_registration(a, (name, scn, noise, scale))
+                assert a["rms"] <= tref.MEASURED[name]["rms"], (scn, noise, scale, a)

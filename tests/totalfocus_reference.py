@@ -132,7 +132,7 @@ def cell_centres(ow: int, oh: int, scale: int):
 
 
 def out_shape(name: str, scale: int):
-    w, h = ref.CASES[name][:2]
+    w, h = ref.case(name)[:2]
     return h // scale, w // scale
 
 
@@ -142,7 +142,7 @@ def truth(name: str, scale: int) -> np.ndarray:
     on the virtual image, whatever the depth)"""
     oh, ow = out_shape(name, scale)
     xu, yu = cell_centres(ow, oh, scale)
-    t = LEVEL * ref.texture()(xu, yu) * float((1 << ref.CASES[name][5]) - 1)
+    t = LEVEL * ref.texture()(xu, yu) * float((1 << ref.case(name)[5]) - 1)
     t.setflags(write=False)
     return t
 
@@ -160,21 +160,21 @@ def true_depth(name: str, scene: str, scale: int) -> np.ndarray:
 @functools.lru_cache(maxsize=None)
 def white_case(name: str) -> np.ndarray:
     """a white image of the case's grid with fall-off inside every disc and vignetting across the sensor"""
-    w, h, d, rot, off, bits, _, _ = ref.CASES[name]
-    tx, ty = white_image.grid_centres(w, h, d, ref.BASE_Y, rot, off, 1.5)
+    w, h, d, _, off, bits, _, _, base_y, _ = ref.case(name)
+    tx, ty = white_image.grid_centres(w, h, d, base_y, ref.grid_rotation(name), off, 1.5)
     wh = white_image.render_white_image(w, h, tx, ty, d, bits=bits, **WHITE)
     wh.setflags(write=False)
     return wh
 
 
 def white_level(name: str) -> int:
-    return int(math.floor(WHITE["level"] * float((1 << ref.CASES[name][5]) - 1) + 0.5))
+    return int(math.floor(WHITE["level"] * float((1 << ref.case(name)[5]) - 1) + 0.5))
 
 
 @functools.lru_cache(maxsize=None)
 def vignetted_case(name: str, scene: str, noise: float) -> np.ndarray:
     """what the sensor records behind lenses that shade like white_case: raw * white / white's level, rounded"""
-    full = float((1 << ref.CASES[name][5]) - 1)
+    full = float((1 << ref.case(name)[5]) - 1)
     raw = ref.make_case(name, scene, noise).astype(np.float64)
     img = np.clip(np.floor(raw * white_case(name).astype(np.float64) / (WHITE["level"] * full) + 0.5), 0.0, full).astype(ref.make_case(name, scene, noise).dtype)
     img.setflags(write=False)
@@ -185,7 +185,7 @@ def vignetted_case(name: str, scene: str, noise: float) -> np.ndarray:
 def interior(name: str, scene: str, scale: int) -> np.ndarray:
     """cells at least ceil(1.5 d / scale) from the border; on `step` without the cells within STEP_EXCLUDE of the step"""
     oh, ow = out_shape(name, scale)
-    m = int(math.ceil(1.5 * ref.CASES[name][2] / scale))
+    m = int(math.ceil(1.5 * ref.case(name)[2] / scale))
     Y, X = np.meshgrid(np.arange(oh), np.arange(ow), indexing="ij")
     inner = (X >= m) & (X <= ow - 1 - m) & (Y >= m) & (Y <= oh - 1 - m)
     if scene == "step":
@@ -198,7 +198,7 @@ def accuracy(name: str, scene: str, tf, scale: int) -> dict:
     """over the status-0 interior cells, as fractions of full scale: RMS of pixel - truth, and the same against truth displaced by
     one cell in +x, -x, +y, -y (the interior keeps a margin, so the displaced cells exist); the share of interior cells with
     status 0 and the fewest lenses among them"""
-    full = float((1 << ref.CASES[name][5]) - 1)
+    full = float((1 << ref.case(name)[5]) - 1)
     inner = interior(name, scene, scale)
     status, image, nl = np.asarray(tf.status), np.asarray(tf.image).astype(np.float64), np.asarray(tf.n_lenses)
     use = inner & (status == OK)
@@ -229,6 +229,10 @@ MEASURED = {
     "d14": dict(rms=0.04972),        # far scene with noise, chained depth, scale 1
     "d23_16": dict(rms=0.05029),     # far scene, true depth with the white image, scale 2
     "d9_pitch": dict(rms=0.05135),   # far scene with noise, chained depth, scale 1
+    # rawdepth_reference.GEOMETRY_CASES: the same over the true and the chained depth, without the white image
+    "d14_rot": dict(rms=0.04971),        # far scene, chained depth, scale 2
+    "d17_sq": dict(rms=0.04993),         # far scene with noise, chained depth, scale 2
+    "d14_rot_off": dict(rms=0.04973),    # far scene with noise, chained depth, scale 1
 }
 BARS = {name: dict(rms=2 * m["rms"]) for name, m in MEASURED.items()}
 
@@ -240,7 +244,7 @@ def run_true(name: str, scene: str, noise: float, gd, scale: int = 1, white: boo
     raw image with its white image"""
     key = ("true", name, scene, noise, scale, white, tuple(sorted(kw.items())))
     if key not in _RENDERS:
-        d = ref.CASES[name][2]
+        d = ref.case(name)[2]
         if white:
             _RENDERS[key] = render(vignetted_case(name, scene, noise), true_depth(name, scene, scale), gd.cx, gd.cy, d, white=white_case(name), scale=scale,
                                    white_level=white_level(name), **kw)
@@ -254,5 +258,5 @@ def run_chained(name: str, scene: str, noise: float, gd, scale: int = 1, **kw):
     key = ("chained", name, scene, noise, scale, tuple(sorted(kw.items())))
     dm = dref.run(name, scene, noise, gd, scale)
     if key not in _RENDERS:
-        _RENDERS[key] = render(ref.make_case(name, scene, noise), dm.inv_depth, gd.cx, gd.cy, ref.CASES[name][2], scale=scale, **kw)
+        _RENDERS[key] = render(ref.make_case(name, scene, noise), dm.inv_depth, gd.cx, gd.cy, ref.case(name)[2], scale=scale, **kw)
     return _RENDERS[key], dm
