@@ -202,8 +202,8 @@ typedef struct lifcal_ba_profile {
   uint32_t n_sweeps;
   double special_points;  /* points worked by the special-point kernels (k_sweep + k_schur: constraints, oversized groups,
                              camera-only / pose-only arities); their time is part of ms_schur, NOT of ms_accumulate        */
-  double ms_accumulate;   /* the dominant kernel of the regular points by its own dispatch time stamps: k_sweep3 (fused residual +
-                             Jacobian + accumulation + point elimination), or k_front4 start to k_back4 end                */
+  double ms_accumulate;   /* the dominant kernel of the regular points by its own dispatch time stamps: k_sweep3 or k_sweep2 (fused
+                             residual + Jacobian + accumulation + point elimination)                                       */
   double ms_schur;        /* ms_total - ms_accumulate: special points, constraints, exchange, k_finalize, gaps (tables: only where the parameters changed) */
   double ms_total;        /* first kernel of the first sweep to the end of the last one, divided by the sweep count    */
   double ms_exchange;     /* world_size > 1: pack + collective + unpack of the partial reduced blocks (part of ms_schur)  */
@@ -392,9 +392,8 @@ int lifcal_ba_plan(const lifcal_ba_problem* p, int32_t rank, int32_t world_size,
 
 /* The schedule of the LDS-window sweep that lifcal_ba_create builds for `rank` with default options in this environment (the same
  * decision code: LIFCAL_SWEEP_KERNEL, LIFCAL_SWEEP_WAVES, LIFCAL_V2_BLOCKS, LIFCAL_GROUP_SPLIT, LIFCAL_DISABLE_V2, LIFCAL_PLAN_COST,
- * LIFCAL_PLAN_BALANCE, and the fallback of LIFCAL_SWEEP_KERNEL=4 to k_sweep3 on frame windows too wide for k_back4), as the
- * planner's cost model sees it.  options.deterministic / options.precision = 1 turn LIFCAL_SWEEP_KERNEL=4 into k_sweep3 at create;
- * this entry point takes no options.  Host-only.  `violations` is recounted from the finished layout arrays, not taken from the
+ * LIFCAL_PLAN_BALANCE), as the planner's cost model sees it.  options.deterministic / options.precision = 1 set four waves per
+ * role at create; this entry point takes no options.  pass_lanes is 256, or 128 with LIFCAL_SWEEP_WAVES=2.  Host-only.  `violations` is recounted from the finished layout arrays, not taken from the
  * planner's own bookkeeping: every regular point in exactly one pass, lanes and points of a pass within their caps, the lanes of a
  * pass sorted by frame (frame-ordered kernels), lane sizes adding up to the observations, a point's and a pass's group ids each one
  * contiguous run that no other point's groups share.  0 on a sound plan.  The block costs are those of the passes as built. */

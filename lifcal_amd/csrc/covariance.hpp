@@ -418,7 +418,7 @@ extern "C" int lifcal_ba_covariance(lifcal_ba_handle* h, const lifcal_ba_covaria
   const uint32_t F = d.F, NA = d.NA, Q3 = 3 * d.Q, nc = d.nc;
   if (h->opt.world_size > 1) { g_last_error = "lifcal_ba_covariance: world_size > 1 is not supported (every rank holds the reduced system: a follow-up)"; return LIFCAL_BA_ERR_INVALID_ARG; }
   if (h->opt.precision != 0) { g_last_error = "lifcal_ba_covariance: options.precision = 1 is not supported; create a second fp64 handle at the solved parameters"; return LIFCAL_BA_ERR_INVALID_ARG; }
-  if (!h->use_sweep3 || h->use_sweep4) { g_last_error = "lifcal_ba_covariance needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; return LIFCAL_BA_ERR_INVALID_ARG; }
+  if (!h->use_sweep3) { g_last_error = "lifcal_ba_covariance needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; return LIFCAL_BA_ERR_INVALID_ARG; }
   const size_t lds2 = (size_t)cov_selinv_lds(d.bw) * 8, lds3 = (size_t)cov_backsolve_lds(d.bw, NA) * 8, lds4 = (size_t)6 * NA * 8;
   if (!h->bandw_ok || lds2 > 160 * 1024 || lds3 > 160 * 1024 || lds4 > 64 * 1024) {
     g_last_error = "lifcal_ba_covariance: the band window (" + std::to_string(d.bw + 1) + " frames, " + std::to_string(NA) + " arrow rows) does not fit LDS; only the LDS-window factorisation is supported";

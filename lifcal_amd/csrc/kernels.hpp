@@ -75,9 +75,6 @@ struct Dev {
   uint32_t n_blocks, v2_nfmax, n_special;
   const uint32_t *blk_pass0, *blk_flo, *blk_nf, *pass_pt0, *pass_np, *pass_gid0, *pass_ng, *v2_points, *v2_ptinfo, *v2_slot, *v2_tile_row0, *v2_lens, *v2f_pt, *v2_passpt, *v2_gidx;
   const double *v2_u, *v2_v;
-  // k_front4 / k_back4 (sweep4.hpp): front workgroup -> block and pass range; block -> range of v2_points
-  uint32_t n_fwg;
-  const uint32_t *fwg_blk, *fwg_pass0, *blk_pt0;
   const float *v2_du, *v2_dv;    // options.precision = 1: observation relative to its micro-lens centre (u - mcx, v - mcy), fp32
   float* ltf;                    // options.precision = 1: fp32 lens table of the CURRENT point (see lens_row_to_float)
   double* ltw;                   // ... and w = (a) c_u of every lens in fp64 (2 per lens): the one fp64 operand of the fp32 evaluation
@@ -474,7 +471,6 @@ LIFCAL_DEV void fold_hot_rows(const Dev& d, uint32_t w) {
 }  // namespace lifcal
 #include "sweep2.hpp"   // k_sweep2: the LDS-window fused sweep (regular points)
 #include "sweep3.hpp"   // k_sweep3: the same with a wave-specialised observation loop (512 threads)
-#include "sweep4.hpp"   // k_front4 + k_back4: the sweep cut in two kernels built for occupancy (LIFCAL_SWEEP_KERNEL=4 only; k_sweep3 is the default)
 namespace lifcal {
 
 // ---------------------------------------------------------------------------------------------

@@ -120,8 +120,6 @@ struct lifcal_ba_handle {
   size_t v2_lds_bytes = 0;
   bool use_sweep3 = true;        // wave-specialised LDS-window kernel (LIFCAL_SWEEP_KERNEL=2 selects k_sweep2)
   int sweep_waves = 4;           // k_sweep3: waves per role, 4 (512 threads, 256-lane passes) or 2 (256 threads, 128-lane passes, two workgroups per CU)
-  bool use_sweep4 = false;       // k_front4 + k_back4 (sweep4.hpp): LIFCAL_SWEEP_KERNEL=4, fp64 and non-deterministic problems only
-  size_t f4_lds = 0, b4_lds = 0; int b4_tpt = 1;
   TileSet ts1{}, ts2{};   // v1 tiles, v2 tiles (flat view)
   double* partial = nullptr;     // 4 doubles + 1 cand cost (all-reduced)
   double* hdiag_tmp = nullptr;
@@ -351,7 +349,7 @@ int launch_value_cost(lifcal_ba_handle* h, const CamConsts* camc, const double* 
 // k_sweep3 (every instantiation) leaves the words all its blocks add to in the copy's hot rows (kernels.hpp: HOT_ROWS) unless the sums
 // are ordered: a mode-0 block of such a handle needs fold_hot_rows before anybody reads those words
 bool uses_hot_rows(const lifcal_ba_handle* h) {
-  return h->d.n_blocks && !h->d.deterministic && !h->use_sweep4 && (h->opt.precision == 1 || h->use_sweep3);
+  return h->d.n_blocks && !h->d.deterministic && (h->opt.precision == 1 || h->use_sweep3);
 }
 int launch_fold_hot(lifcal_ba_handle* h) {
   if (!uses_hot_rows(h)) return 0;
@@ -370,17 +368,7 @@ int launch_blocks(lifcal_ba_handle* h, double radius, int mode) {
   // kernel's dispatch packet itself) — event records around it are separate barrier packets, ~2 us of idle queue each, four per sweep
   const bool prof = mode == 0 && h->prof_active();
   hipEvent_t ev_a = prof ? h->prof_ev(1) : nullptr, ev_b = prof ? h->prof_ev(2) : nullptr;
-  if (d.n_blocks && h->use_sweep4) {   // regular points: observations -> blocks (k_front4), then the point elimination per block (k_back4)
-#define CALL_FRONT4(NR, TAN, ADJ) hipExtLaunchKernelGGL((k_front4<NR, TAN, ADJ>), dim3(d.n_fwg), dim3(F4_THREADS), h->f4_lds, h->stream, ev_a, mode == 0 ? nullptr : ev_b, 0, d, mode)
-    DISPATCH_CFG(h, CALL_FRONT4);
-#undef CALL_FRONT4
-    if (mode == 0) {
-#define CALL_BACK4(NCV) do { if (h->b4_tpt == 1) hipExtLaunchKernelGGL((k_back4<NCV, 1>), dim3(d.n_blocks), dim3(B4_THREADS), h->b4_lds, h->stream, nullptr, ev_b, 0, d, radius); \
-                             else hipExtLaunchKernelGGL((k_back4<NCV, 2>), dim3(d.n_blocks), dim3(B4_THREADS), h->b4_lds, h->stream, nullptr, ev_b, 0, d, radius); } while (0)
-      switch (d.nc) { case 5: CALL_BACK4(5); break; case 6: CALL_BACK4(6); break; case 7: CALL_BACK4(7); break; case 8: CALL_BACK4(8); break; default: CALL_BACK4(9); break; }
-#undef CALL_BACK4
-    }
-  } else if (d.n_blocks) {   // regular points: LDS-window kernel, one workgroup per block
+  if (d.n_blocks) {   // regular points: LDS-window kernel, one workgroup per block
     hipEvent_t ev_stop = d.deterministic ? nullptr : ev_b;   // (deterministic: the slab reduction below belongs to the dominant work)
 #define LAUNCH_DOM(KERNEL, THREADS) hipExtLaunchKernelGGL(KERNEL, dim3(d.n_blocks), dim3(THREADS), h->v2_lds_bytes, h->stream, ev_a, ev_stop, 0, d, radius, mode)
 #define CALL_SWEEP2(NR, TAN, ADJ) LAUNCH_DOM((k_sweep2<NR, TAN, ADJ>), 256)
@@ -808,17 +796,14 @@ int lifcal_init_plenoptic(const lifcal_init_problem* p, int32_t device, lifcal_i
   return 0;
 }
 
-// the sweep implementation for regular points (LIFCAL_SWEEP_KERNEL): 3 = k_sweep3 (default), 2 = k_sweep2, 4 = k_front4 + k_back4
-// (sweep4.hpp: the two-kernel, pipelined-evaluator design of round 3 — parity green, measured slower than k_sweep3: DESIGN.md 4.5)
+// the sweep implementation for regular points (LIFCAL_SWEEP_KERNEL): 3 = k_sweep3 (default), 2 = k_sweep2; any other value means the default
 static int sweep_kernel_from_env() {
   const char* e = getenv("LIFCAL_SWEEP_KERNEL");
-  const int k = e ? atoi(e) : 3;
-  return (k == 2 || k == 4) ? k : 3;
+  return e && atoi(e) == 2 ? 2 : 3;
 }
-// the planner's layout for a kernel choice: lanes per pass and number of blocks
-static void sweep_layout(int kernel, int waves, uint32_t* pass_lanes, uint32_t* blocks) {
-  if (kernel == 4) { *pass_lanes = 64u; *blocks = 256u; }
-  else { *pass_lanes = waves == 2 ? 128u : 256u; *blocks = waves == 2 ? 512u : 256u; }
+// the planner's layout for the waves per role: lanes per pass and number of blocks
+static void sweep_layout(int waves, uint32_t* pass_lanes, uint32_t* blocks) {
+  *pass_lanes = waves == 2 ? 128u : 256u; *blocks = waves == 2 ? 512u : 256u;
 }
 
 // k_sweep3's waves per role: LIFCAL_SWEEP_WAVES = 2 | 4 (k_sweep2 always works on 256-lane passes)
@@ -843,18 +828,13 @@ int lifcal_init_plenoptic_recalibration(double fL_fixed, double B_fixed, lifcal_
 //   LIFCAL_V2_BLOCKS     workgroups the LDS-window sweep is cut into (default: one per CU)
 //   LIFCAL_GROUP_SPLIT   observations per lane above which a (point, frame) group is cut into several lanes (0 = never; default:
 //                        chosen per block by the planner's cost model)
-struct PlanChoice { bool use_sweep3 = true, use_sweep4 = false; int sweep_waves = 4, b4_tpt = 1; };
+struct PlanChoice { bool use_sweep3 = true; int sweep_waves = 4; };
 static int plan_for_environment(const lifcal_ba_problem* p, int rank, int world, int deterministic, int precision, const lifcal_ba_partition* part, Plan* pl, PlanChoice* c,
                                 const std::vector<uint32_t>* prior_points = nullptr) {
   const bool enable_v2 = getenv("LIFCAL_DISABLE_V2") == nullptr;
   // the wave-specialised kernel wants the lanes of a pass sorted by frame, k_sweep2 (LIFCAL_SWEEP_KERNEL=2) by point
-  int kernel = sweep_kernel_from_env();
-  // ordered reductions and the fp32 evaluation exist in k_sweep3 only
-  if (kernel == 4 && (deterministic == 1 || precision == 1)) kernel = 3;
-  c->use_sweep3 = kernel != 2;   // (frame-ordered lanes: k_sweep3 and k_front4)
-  c->use_sweep4 = kernel == 4;
-  c->sweep_waves = sweep_waves_from_env(kernel == 3);
-  c->b4_tpt = 1;
+  c->use_sweep3 = sweep_kernel_from_env() != 2;
+  c->sweep_waves = sweep_waves_from_env(c->use_sweep3);
   if (deterministic == 1) {
     if (!c->use_sweep3) { g_last_error = "options.deterministic = 1 needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; return LIFCAL_BA_ERR_INVALID_ARG; }
     c->sweep_waves = 4;
@@ -864,24 +844,10 @@ static int plan_for_environment(const lifcal_ba_problem* p, int rank, int world,
     if (!c->use_sweep3) { g_last_error = "options.precision = 1 needs k_sweep3 (unset LIFCAL_SWEEP_KERNEL)"; return LIFCAL_BA_ERR_INVALID_ARG; }
     c->sweep_waves = 4;
   }
-  uint32_t plan_lanes, plan_blocks; sweep_layout(kernel, c->sweep_waves, &plan_lanes, &plan_blocks);
+  uint32_t plan_lanes, plan_blocks; sweep_layout(c->sweep_waves, &plan_lanes, &plan_blocks);
   const uint32_t v2_blocks = getenv("LIFCAL_V2_BLOCKS") ? (uint32_t)std::max(1, atoi(getenv("LIFCAL_V2_BLOCKS"))) : plan_blocks;
   const uint32_t split_obs = getenv("LIFCAL_GROUP_SPLIT") ? (uint32_t)std::max(0, atoi(getenv("LIFCAL_GROUP_SPLIT"))) : UINT32_MAX;
-  if (int rc = build_plan(p, rank, world, pl, enable_v2, v2_blocks, split_obs, c->use_sweep3, plan_lanes, precision == 1, part, prior_points)) return rc;
-  if (c->use_sweep4) {
-    // k_back4 keeps at most two 4x4 tiles of the window per thread of a 256-thread group: wider frame windows take k_sweep3
-    uint32_t max_ntri = 0;
-    for (uint32_t b = 0; b < pl->n_blocks; ++b) max_ntri = std::max(max_ntri, V4Back::ntri_of(pl->blk_nf[b], (uint32_t)pl->nc));
-    if (max_ntri > 512) {
-      c->use_sweep4 = false; c->sweep_waves = 4;
-      sweep_layout(3, 4, &plan_lanes, &plan_blocks);
-      *pl = Plan();
-      if (int rc = build_plan(p, rank, world, pl, enable_v2, getenv("LIFCAL_V2_BLOCKS") ? v2_blocks : plan_blocks, split_obs, true, plan_lanes, false, part, prior_points)) return rc;
-    } else {
-      c->b4_tpt = max_ntri > 256 ? 2 : 1;
-    }
-  }
-  return 0;
+  return build_plan(p, rank, world, pl, enable_v2, v2_blocks, split_obs, c->use_sweep3, plan_lanes, precision == 1, part, prior_points);
 }
 
 static void fill_plan_info(const Plan& pl, lifcal_ba_plan_info* info) {
@@ -968,7 +934,7 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
     if (pp) h->pp_point.assign(pp->point, pp->point + pp->n);   // (checked by the caller: ascending, below n_points)
     const int rc = plan_for_environment(p, opt.rank, opt.world_size, opt.deterministic, opt.precision, part, &h->plan, &c, pp ? &h->pp_point : nullptr);
     if (rc) { delete h; return rc; }
-    h->use_sweep3 = c.use_sweep3; h->use_sweep4 = c.use_sweep4; h->sweep_waves = c.sweep_waves; h->b4_tpt = c.b4_tpt;
+    h->use_sweep3 = c.use_sweep3; h->sweep_waves = c.sweep_waves;
   }
   cclk.lap("create: plan");
   h->prob = *p;
@@ -977,20 +943,17 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
     g_last_error = "no HIP device available: the bundle-adjustment path has no CPU fallback"; delete h; return LIFCAL_BA_ERR_NO_DEVICE;
   }
   if (hipSetDevice(opt.device) != hipSuccess) { g_last_error = "hipSetDevice failed"; delete h; return LIFCAL_BA_ERR_NO_DEVICE; }
-  int n_cus = 0;
   {
     // the architecture of a device ordinal does not change while the process lives: hipGetDeviceProperties costs ~3 ms per call
     static std::mutex arch_mutex;
     static std::string arch_name[64];
-    static int arch_cus[64];
     std::lock_guard<std::mutex> lock(arch_mutex);
     std::string& name = arch_name[opt.device & 63];
     if (name.empty() || opt.device >= 64) {
       hipDeviceProp_t prop;
       if (hipGetDeviceProperties(&prop, opt.device) != hipSuccess) { delete h; return LIFCAL_BA_ERR_NO_DEVICE; }
-      name = prop.gcnArchName; arch_cus[opt.device & 63] = prop.multiProcessorCount;
+      name = prop.gcnArchName;
     }
-    n_cus = arch_cus[opt.device & 63];
     if (std::strncmp(name.c_str(), "gfx950", 6) != 0) {
       g_last_error = std::string("device is ") + name + ", this library carries gfx950 code objects only"; delete h; return LIFCAL_BA_ERR_NO_DEVICE;
     }
@@ -1040,16 +1003,12 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
   for (uint32_t b = 0; b < L.n_blocks; ++b) {
     const uint32_t ncolp = ((6 * L.blk_nf[b] + (uint32_t)L.nc + 1) + 15u) & ~15u;
     for (uint32_t ps = L.blk_pass0[b]; ps < L.blk_pass0[b + 1]; ++ps)
-      if ((!h->use_sweep4 && (size_t)((3 * L.pass_np[ps] + 7u) & ~7u) * (ncolp + 2) > L.zd_doubles()) || L.pass_ng[ps] > L.pass_lanes || L.pass_np[ps] > L.np_max()) {
+      if ((size_t)((3 * L.pass_np[ps] + 7u) & ~7u) * (ncolp + 2) > L.zd_doubles() || L.pass_ng[ps] > L.pass_lanes || L.pass_np[ps] > L.np_max()) {
         g_last_error = "internal: a planned pass does not fit the LDS window";
         return fail(LIFCAL_BA_ERR_INVALID_ARG);
       }
   }
   h->v2_lds_bytes = (size_t)V2Lds(d.v2_nfmax, h->use_sweep3, L.pass_lanes).total * sizeof(double);
-  if (h->use_sweep4) {
-    h->f4_lds = (size_t)V4Front(d.v2_nfmax).total * sizeof(double);
-    h->b4_lds = (size_t)V4Back(d.v2_nfmax).total * sizeof(double);
-  }
   d.deterministic = opt.deterministic == 1 ? 1u : 0u;
   if (d.deterministic) {
     d.det_stride = (V2Lds(d.v2_nfmax, true, 256).off_fr + 3u + 1u) & ~1u;
@@ -1057,43 +1016,7 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
     A(d.det_slots, 4 * (size_t)std::max<uint32_t>(1024u, (std::max(4 * d.n_owned, d.Q) + 255u) / 256u));
     A(d.det_turn, 4);
   }
-  if (d.n_blocks && h->use_sweep4) {
-    // k_front4: as many workgroups as the chip holds at once (each walks a contiguous share of one block's tiles)
-    int per_cu = 0;
-#define SET_F4(NR, TAN, ADJ) do { if (hipFuncSetAttribute((const void*)k_front4<NR, TAN, ADJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->f4_lds) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP); \
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, (const void*)k_front4<NR, TAN, ADJ>, (int)F4_THREADS, h->f4_lds) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP); } while (0)
-    DISPATCH_CFG(h, SET_F4);
-#undef SET_F4
-#define SET_B4(NCV) do { if (hipFuncSetAttribute((const void*)k_back4<NCV, 1>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->b4_lds) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP); \
-    if (hipFuncSetAttribute((const void*)k_back4<NCV, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->b4_lds) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP); } while (0)
-    switch (d.nc) { case 5: SET_B4(5); break; case 6: SET_B4(6); break; case 7: SET_B4(7); break; case 8: SET_B4(8); break; default: SET_B4(9); break; }
-#undef SET_B4
-    per_cu = std::max(1, std::min(per_cu, 5));
-    if (const char* e = getenv("LIFCAL_F4_PER_CU")) per_cu = std::max(1, atoi(e));
-    const uint32_t capacity = (uint32_t)per_cu * (uint32_t)std::max(1, n_cus);
-    const uint32_t parts = std::max(1u, capacity / std::max(1u, d.n_blocks));
-    std::vector<uint32_t> fwg_blk, fwg_pass0, blk_pt0(L.n_blocks + 1, 0);
-    for (uint32_t b = 0; b < L.n_blocks; ++b) {
-      const uint32_t p0 = L.blk_pass0[b], p1 = L.blk_pass0[b + 1];
-      blk_pt0[b] = p0 < L.n_passes ? L.pass_pt0[p0] : (uint32_t)L.v2_points.size();
-      // a tile costs its observation steps plus a fixed share (emission, gather): cut the block's tiles into `parts` equal runs
-      auto tile_cost = [&](uint32_t ps) { return (uint64_t)(L.v2_tile_row0[ps + 1] - L.v2_tile_row0[ps]) + 3u; };
-      uint64_t total = 0;
-      for (uint32_t ps = p0; ps < p1; ++ps) total += tile_cost(ps);
-      const uint32_t np = std::min(parts, std::max(1u, p1 - p0));
-      uint64_t acc = 0; uint32_t next = 0;
-      for (uint32_t ps = p0; ps < p1; ++ps) {
-        if (next < np && acc * np >= (uint64_t)next * total) { fwg_blk.push_back(b); fwg_pass0.push_back(ps); ++next; }
-        acc += tile_cost(ps);
-      }
-    }
-    blk_pt0[L.n_blocks] = (uint32_t)L.v2_points.size();
-    fwg_pass0.push_back(L.n_passes);
-    d.n_fwg = (uint32_t)fwg_blk.size();
-    if (cclk.on) std::fprintf(stderr, "[create] k_front4: %d workgroups per CU (occupancy API), %u workgroups over %u blocks, LDS %zu B; k_back4: LDS %zu B, %d tile(s) per thread\n",
-                              per_cu, d.n_fwg, d.n_blocks, h->f4_lds, h->b4_lds, h->b4_tpt);
-    { uint32_t* t; U(t, fwg_blk); d.fwg_blk = t; U(t, fwg_pass0); d.fwg_pass0 = t; U(t, blk_pt0); d.blk_pt0 = t; }
-  } else if (d.n_blocks) {
+  if (d.n_blocks) {
 #define SET_LDS(NR, TAN, ADJ) do { if (hipFuncSetAttribute((const void*)k_sweep2<NR, TAN, ADJ>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->v2_lds_bytes) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP); \
     if (hipFuncSetAttribute((const void*)k_sweep3<NR, TAN, ADJ, 4>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->v2_lds_bytes) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP); \
     if (hipFuncSetAttribute((const void*)k_sweep3<NR, TAN, ADJ, 2>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)h->v2_lds_bytes) != hipSuccess) return fail(LIFCAL_BA_ERR_HIP); \
@@ -1142,7 +1065,7 @@ static int create_impl(const lifcal_ba_problem* p, const lifcal_ba_options* o, l
       h->xch_ok = true;
     }
   }
-  A(d.dbg, std::max((size_t)std::max(1u, d.n_blocks) * 32, (size_t)d.n_fwg * 64));
+  A(d.dbg, (size_t)std::max(1u, d.n_blocks) * 32);
   A(d.dP, 3 * (size_t)d.P); A(h->ls_buf, 8); A(h->dirmax_buf, 65); A(d.lm, LM_N);
   A(h->hdiag_tmp, d.n_red); A(h->stats_buf, 8); A(h->stats_slots, 4 + 2 * 64); A(h->pts_gather, 3 * (size_t)d.P);
   // Cholesky panel: LDS when it fits (<= 64 KiB by default launch limits), else a global scratch
@@ -1274,11 +1197,6 @@ int lifcal_ba_comm_init_rccl(lifcal_ba_handle* h, const void* unique_id128) {
 extern "C" int lifcal_ba_debug_stamps(lifcal_ba_handle* h, unsigned long long* out, uint32_t max_blocks) {
   if (!h || !out) return LIFCAL_BA_ERR_INVALID_ARG;
   HIP_TRY(hipStreamSynchronize(h->stream));
-  if (h->use_sweep4) {   // k_front4: 64 counters per front workgroup (16 per role)
-    const uint32_t n = std::min(max_blocks / 2, h->d.n_fwg);
-    HIP_TRY(hipMemcpy(out, h->d.dbg, (size_t)n * 64 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    return (int)n;
-  }
   const uint32_t n = std::min(max_blocks, h->d.n_blocks);
   HIP_TRY(hipMemcpy(out, h->d.dbg, (size_t)n * 32 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
   return (int)n;

@@ -31,7 +31,7 @@ sc = scene.make_scene(S(%s))
 pa = capi.ProblemArrays.from_scene(sc)
 st = lifcal_amd.plan_stats(pa)
 if %d:
-    assert st.pass_lanes == %d, st.pass_lanes   # the kernel asked for is the one the plan was made for (no fallback to k_sweep3)
+    assert st.pass_lanes == 256, st.pass_lanes   # the plan of the default kernel, k_sweep3 with four waves per role
     assert st.violations == 0 and st.n_points_permuted > 0 and st.n_blocks >= 2 and st.max_block_passes >= 2, (st.violations, st.n_points_permuted, st.n_blocks, st.max_block_passes)
 with BundleAdjustment(pa) as ba:
     r = ba.sweep(123.0, want_matrices=True)
@@ -44,7 +44,7 @@ def run_child(out_dir, spec_args, env_extra, tag, balanced):
     out = os.path.join(str(out_dir), tag + ".npz")
     env = dict(os.environ); env.update(env_extra)
     env.pop("LIFCAL_PLAN_BALANCE", None)
-    subprocess.check_call([sys.executable, "-c", _CHILD % (ROOT, spec_args, 1 if balanced else 0, 64 if env_extra.get("LIFCAL_SWEEP_KERNEL") == "4" else 256), out], env=env, cwd=ROOT)
+    subprocess.check_call([sys.executable, "-c", _CHILD % (ROOT, spec_args, 1 if balanced else 0), out], env=env, cwd=ROOT)
     return np.load(out)
 
 
@@ -58,8 +58,7 @@ def atomic_reference(built, tmp_path_factory):
 @pytest.mark.parametrize("spec_args,env", [
     (PLAIN, {"LIFCAL_V2_BLOCKS": "3"}),
     (CONSTRAINED, {"LIFCAL_V2_BLOCKS": "3"}),
-    (PLAIN, {"LIFCAL_V2_BLOCKS": "3", "LIFCAL_SWEEP_KERNEL": "4"}),
-], ids=["three_blocks", "three_blocks_constraints", "three_blocks_two_kernel_sweep"])
+], ids=["three_blocks", "three_blocks_constraints"])
 def test_sweep_on_the_balanced_plan_equals_the_atomic_path(built, tmp_path, atomic_reference, spec_args, env):
     a = run_child(tmp_path, spec_args, env, "bal", True)
     b = atomic_reference[spec_args]

@@ -105,12 +105,12 @@ OFF_DEFAULT_CASES = [
     Case("scale_3", od.SCALE_3, LDS_CHAIN, **E),
     Case("scale_3_aniso_125", od.SCALE_3, LDS_CHAIN, transform=ANISO, **E),
 ] + [Case(name, od.ROBUST, LDS_CHAIN, options={"loss_scale": ls}, **E) for name, ls in od.LOSS_SCALES.items()] + CLAMP_CASES
-# the clamp cases and aniso_125 once more per damping site of the full sweep: k_sweep2, k_front4 + k_back4, the global-atomic kernels
+# the clamp cases and aniso_125 once more per damping site of the full sweep: k_sweep2, the global-atomic kernels
 # with k_schur, and k_sweep3 with two waves per role (all fp64 and unordered: no pairing here that create() refuses or redirects)
-SWEEP_SETTINGS = [{"LIFCAL_SWEEP_KERNEL": "2"}, {"LIFCAL_SWEEP_KERNEL": "4"}, {"LIFCAL_DISABLE_V2": "1"}, {"LIFCAL_SWEEP_WAVES": "2"}]
-# lanes per pass of the plan create() makes in each of them (lifcal_ba_plan_stats: 64 is k_front4 + k_back4, 128 k_sweep3 with two
-# waves per role, 256 k_sweep3 and k_sweep2), so that a fallback to k_sweep3 cannot take a case's damping site away unnoticed
-PASS_LANES = {"LIFCAL_SWEEP_KERNEL": {"2": 256, "4": 64}, "LIFCAL_SWEEP_WAVES": {"2": 128}}
+SWEEP_SETTINGS = [{"LIFCAL_SWEEP_KERNEL": "2"}, {"LIFCAL_DISABLE_V2": "1"}, {"LIFCAL_SWEEP_WAVES": "2"}]
+# lanes per pass of the plan create() makes in each of them (lifcal_ba_plan_stats: 128 is k_sweep3 with two waves per role, 256 k_sweep3
+# and k_sweep2), so that a fallback to k_sweep3 cannot take a case's damping site away unnoticed
+PASS_LANES = {"LIFCAL_SWEEP_KERNEL": {"2": 256}, "LIFCAL_SWEEP_WAVES": {"2": 128}}
 OFF_DEFAULT_CASES += [dataclasses.replace(c, id=c.id + "_" + "_".join(f"{k[7:].lower()}_{v}" for k, v in env.items()), env=env)
                       for env in SWEEP_SETTINGS for c in CLAMP_CASES + [ANISO_125]]
 

@@ -18,8 +18,8 @@ SCENES = {
     "w8_f30_300_points": S(30, 300, 8, 0xF06, 1204, outlier_fraction=0.02),
     "w8_f40_2500_points": scene.SceneSpec(40, 2500, 8, 0xF06, 4242, outlier_fraction=0.02),
 }
-# (LIFCAL_SWEEP_KERNEL, LIFCAL_SWEEP_WAVES): 256-lane frame-ordered passes, point-ordered passes, 64-lane passes, 128-lane passes
-LAYOUTS = [("3", None), ("2", None), ("4", None), ("3", "2")]
+# (LIFCAL_SWEEP_KERNEL, LIFCAL_SWEEP_WAVES): 256-lane frame-ordered passes, point-ordered passes, 128-lane passes
+LAYOUTS = [("3", None), ("2", None), ("3", "2")]
 BLOCKS = [None, "1", "3", "64"]
 
 
@@ -35,7 +35,7 @@ def test_layout_contracts_hold_for_every_plan(built, monkeypatch, name):
     """every regular point in exactly one pass, lanes <= pass_lanes, points <= the block's Z-matrix cap, lanes sorted by frame, lane
     sizes adding up to the observations, group ids of a point and of a pass one run each with no special point's groups inside"""
     pa = problem(scene.make_scene(SCENES[name]))
-    permuted = lanes64 = 0
+    permuted = 0
     for balance, (kernel, waves), blocks in itertools.product((None, "0"), LAYOUTS, BLOCKS):
         _setenv(monkeypatch, "LIFCAL_PLAN_BALANCE", balance)
         _setenv(monkeypatch, "LIFCAL_SWEEP_KERNEL", kernel)
@@ -44,11 +44,7 @@ def test_layout_contracts_hold_for_every_plan(built, monkeypatch, name):
         st = lifcal_amd.plan_stats(pa)
         tag = (name, balance, kernel, waves, blocks)
         assert st.violations == 0, tag
-        if kernel == "4":   # (a block window too wide for k_back4 sends the whole problem to k_sweep3, as at create: 20 frames with 9 camera slots)
-            assert st.pass_lanes in (64, 256), tag
-            lanes64 += st.pass_lanes == 64
-        else:
-            assert st.pass_lanes == (128 if waves == "2" else 256), tag
+        assert st.pass_lanes == (128 if waves == "2" else 256), tag
         assert st.n_blocks >= 1 and st.n_passes >= st.n_blocks and st.n_obs_window > 0, tag
         if balance == "0":
             assert st.n_points_permuted == 0, tag
@@ -58,7 +54,6 @@ def test_layout_contracts_hold_for_every_plan(built, monkeypatch, name):
     # the scenes with several points per pass and mixed pair sizes must actually exercise the new order
     if name in ("w8_f30_300_points", "w8_f40_2500_points", "windowed"):
         assert permuted > 0
-    assert lanes64 >= 2   # the 64-lane plan was really built, in both orders
 
 
 @pytest.fixture(scope="module")
@@ -111,3 +106,22 @@ def test_planner_threads_do_not_change_the_balanced_layout(built, capfd, monkeyp
         assert st.violations == 0 and st.n_points_permuted > 0
         seen[threads] = (m.group(1), st.n_blocks, st.n_passes, st.n_lanes, st.pass_steps, st.block_cost_max)
     assert seen["1"] == seen["3"] == seen["8"]
+
+
+def test_unknown_sweep_kernel_values_plan_like_the_default(built, capfd, monkeypatch):
+    """LIFCAL_SWEEP_KERNEL knows 2; every other value (4 named a kernel pair that is gone) is the default: 256-lane passes and the
+    layout fingerprint (LIFCAL_PLAN_HASH) of the plan built with the variable unset"""
+    pa = problem(scene.make_scene(SCENES["w8_f30_300_points"]))
+    for var in ("LIFCAL_SWEEP_WAVES", "LIFCAL_V2_BLOCKS", "LIFCAL_GROUP_SPLIT", "LIFCAL_PLAN_COST", "LIFCAL_PLAN_BALANCE", "LIFCAL_DISABLE_V2"):
+        monkeypatch.delenv(var, raising=False)
+    monkeypatch.setenv("LIFCAL_PLAN_HASH", "1")
+    seen = {}
+    for kernel in (None, "4", "junk"):
+        _setenv(monkeypatch, "LIFCAL_SWEEP_KERNEL", kernel)
+        capfd.readouterr()
+        st = lifcal_amd.plan_stats(pa)
+        m = re.search(r"\[plan\] hash ([0-9a-f]{16})", capfd.readouterr().err)
+        assert m
+        assert st.violations == 0 and st.pass_lanes == 256, kernel
+        seen[kernel] = m.group(1)
+    assert seen["4"] == seen[None] and seen["junk"] == seen[None], seen
