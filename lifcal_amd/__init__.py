@@ -18,3 +18,4 @@ from .raw_depth import estimateRawDepth, checkRawDepth, RawDepth, RawPoints  # n
 from .depth_map import depthMapFromRaw, checkDepthMap, VirtualDepthMap  # noqa: F401
 from .total_focus import totalFocusImage, checkTotalFocus, TotalFocusImage  # noqa: F401
 from .features import detectFeatures, matchFeatures, linkTracks, trackSequence, checkFeatures, Features, Matches, Tracks  # noqa: F401
+from .verify import featurePoints, verifyMatches, checkVerify, FeaturePoints, Verification  # noqa: F401

@@ -617,6 +617,34 @@ FEATURES_PROTOTYPES = {
     "lifcal_tracks_link": (C.c_int, [C.c_uint32, uptr, C.c_uint32, uptr, C.POINTER(C.c_uint64), uptr, uptr, C.POINTER(Tracks)]),
 }
 
+class VerifyPoints(C.Structure):        # include/lifcal_verify.h lifcal_verify_points
+    _fields_ = [("n_frames", C.c_uint32), ("reserved", C.c_uint32), ("offset", uptr), ("xyz", dptr), ("tol_lat", dptr), ("tol_dep", dptr)]
+
+
+class VerifyOptions(C.Structure):       # lifcal_verify_options
+    _fields_ = [("hypotheses", C.c_uint32), ("seed", C.c_uint32), ("min_inliers", C.c_int32), ("refine", C.c_int32), ("min_ratio", C.c_double)]
+
+
+class VerifyPair(C.Structure):          # lifcal_verify_pair
+    _fields_ = [("status", C.c_uint32), ("n_matches", C.c_uint32), ("n_usable", C.c_uint32), ("best_hypothesis", C.c_uint32),
+                ("n_inliers_hypothesis", C.c_uint32), ("n_inliers", C.c_uint32), ("rounds_used", C.c_uint32), ("reserved", C.c_uint32),
+                ("R", C.c_double * 9), ("t", C.c_double * 3), ("rms", C.c_double)]
+
+
+class VerifyResult(C.Structure):        # lifcal_verify_result
+    _fields_ = [("keep", C.POINTER(C.c_uint8)), ("e_par", dptr), ("e_perp", dptr), ("pair", C.POINTER(VerifyPair)), ("seconds", C.c_double)]
+
+
+_u64ptr = C.POINTER(C.c_uint64)
+
+# every symbol include/lifcal_verify.h declares
+VERIFY_PROTOTYPES = {
+    "lifcal_matches_verify_check": (C.c_int, [C.POINTER(VerifyPoints), C.c_uint32, uptr, _u64ptr, uptr, uptr, C.POINTER(VerifyOptions),
+                                              C.POINTER(VerifyOptions)]),
+    "lifcal_matches_verify": (C.c_int, [C.POINTER(VerifyPoints), C.c_uint32, uptr, _u64ptr, uptr, uptr, C.c_int32, C.POINTER(VerifyOptions),
+                                        C.POINTER(VerifyResult)]),
+}
+
 # every symbol include/lifcal_prior.h declares
 PRIOR_PROTOTYPES = {
     "lifcal_ba_check_point_priors": (C.c_int, [C.c_uint32, C.POINTER(PointPriors)]),
@@ -729,7 +757,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()) + list(TOTALFOCUS_PROTOTYPES.items()) + list(FEATURES_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()) + list(TOTALFOCUS_PROTOTYPES.items()) + list(FEATURES_PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args

@@ -81,6 +81,16 @@ class Matches:
         s = slice(int(self.pair_start[p]), int(self.pair_start[p + 1]))
         return self.i[s], self.j[s], self.dist[s]
 
+    def filtered(self, keep) -> "Matches":
+        """the matches with a true `keep` (one entry per match, Verification.keep as it is), pair_start recomputed; linkTracks
+        takes the result as it takes this"""
+        keep = np.asarray(keep).astype(bool).reshape(-1)
+        if len(keep) != len(self.i):
+            raise ValueError("Matches.filtered: one entry per match")
+        start = np.asarray(self.pair_start, np.int64)
+        kept = np.concatenate([[0], np.cumsum(keep)])
+        return Matches(self.pairs, kept[start].astype(np.uint64), self.i[keep], self.j[keep], self.dist[keep], self.seconds)
+
 
 @dataclass
 class Tracks:
@@ -216,13 +226,32 @@ def linkTracks(features, matches: Matches, min_length: int = 2) -> Tracks:
     return Tracks(fr, pt, ft, x[ft], y[ft], int(t.n_tracks), int(t.n_conflicts))
 
 
-def trackSequence(images, statuses=None, window: int = 2, min_length: int = 2, device: int = 0, detect=None, match=None):
+def trackSequence(images, statuses=None, window: int = 2, min_length: int = 2, device: int = 0, detect=None, match=None, verify=None):
     """detectFeatures on every image (with its status map when statuses is given), matchFeatures over every frame and the next
-    `window`, linkTracks.  detect, match: dicts of options.  Returns (features, matches, tracks)."""
+    `window`, linkTracks.  detect, match: dicts of options.  Returns (features, matches, tracks).
+
+    verify: None, or a dict that asks for the geometric verification of the matches (lifcal_amd.verify) before they are linked.
+    It holds either `points`, a callable that takes the features and returns their FeaturePoints (or the FeaturePoints
+    themselves), or the arguments of featurePoints after `features` (depth_maps, cam, config, spx, ...); `options`: a dict of
+    verifyMatches options.  Then the tracks are those of the kept matches and the return value is (features, matches, tracks,
+    verification), with `matches` still the unfiltered ones (matches.filtered(verification.keep) are the linked ones)."""
     images = list(images)
     statuses = [None] * len(images) if statuses is None else list(statuses)
     if len(statuses) != len(images):
         raise ValueError("trackSequence: one status map per image, or none")
     feats = [detectFeatures(im, st, device=device, **(detect or {})) for im, st in zip(images, statuses)]
     m = matchFeatures(feats, window=window, device=device, **(match or {}))
-    return feats, m, linkTracks(feats, m, min_length)
+    if verify is None:
+        return feats, m, linkTracks(feats, m, min_length)
+    from . import verify as _verify
+    args = dict(verify)
+    options = args.pop("options", None) or {}
+    if "points" in args:
+        points = args.pop("points")
+        if args:
+            raise TypeError(f"trackSequence: verify holds `points` and also {sorted(args)}")
+        points = points(feats) if callable(points) else points
+    else:
+        points = _verify.featurePoints(feats, device=device, **args)
+    v = _verify.verifyMatches(points, m, device=device, **options)
+    return feats, m, linkTracks(feats, m.filtered(v.keep), min_length), v
