@@ -22,7 +22,8 @@
  * detail of libstdc++; here frames are in ascending image id and points in ascending point3D id (any order gives the same
  * calibration problem).  A 2D point that references a 3D point id missing from points3D is an error here
  * (LIFCAL_BA_ERR_OUT_OF_RANGE); the reference silently maps it to point 0 through std::map::operator[].
- * Not part of this row: ReduceNumberPoints, ArUco markers, scaling by the first constraint (:199-487).
+ * Not part of this row: ReduceNumberPoints (:199-310).  Markers, the constraints file and the scaling by the first constraint
+ * (:314-487) are include/lifcal_markers.h.
  */
 #ifndef LIFCAL_COLMAP_H
 #define LIFCAL_COLMAP_H

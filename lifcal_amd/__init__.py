@@ -19,3 +19,5 @@ from .depth_map import depthMapFromRaw, checkDepthMap, VirtualDepthMap  # noqa: 
 from .total_focus import totalFocusImage, checkTotalFocus, TotalFocusImage  # noqa: F401
 from .features import detectFeatures, matchFeatures, linkTracks, trackSequence, checkFeatures, Features, Matches, Tracks  # noqa: F401
 from .verify import featurePoints, verifyMatches, checkVerify, FeaturePoints, Verification  # noqa: F401
+from .markers import (Dictionary, Markers, MarkerComponents, ConstraintList, checkMarkers, detectMarkers, markerComponents, detectMarkerSequence,  # noqa: F401
+                      readConstraints, addMarkers, mergePoints, MarkedTracks, seedMarkerPoints, sceneScaleFactor, scaleScene)

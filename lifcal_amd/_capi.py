@@ -645,6 +645,58 @@ VERIFY_PROTOTYPES = {
                                         C.POINTER(VerifyResult)]),
 }
 
+class MarkerDictionary(C.Structure):    # include/lifcal_markers.h lifcal_marker_dictionary
+    _fields_ = [("marker_bits", C.c_int32), ("n", C.c_uint32), ("words", C.POINTER(C.c_uint64))]
+
+
+class MarkersOptions(C.Structure):      # lifcal_markers_options
+    _fields_ = [("w", C.c_int32), ("contrast", C.c_int32), ("cell_contrast", C.c_int32), ("min_area", C.c_int32), ("min_side", C.c_int32),
+                ("max_side", C.c_int32), ("max_border_errors", C.c_int32), ("max_correction", C.c_int32), ("refine_max", C.c_double)]
+
+
+class MarkersPlan(C.Structure):         # lifcal_markers_plan
+    _fields_ = [("options", MarkersOptions), ("min_distance", C.c_int32), ("tiles_x", C.c_int32), ("tiles_y", C.c_int32), ("reserved", C.c_int32),
+                ("max_candidates", C.c_int64)]
+
+
+# lifcal_marker and lifcal_marker_component as numpy record types (the lists are arrays of these)
+MARKER_DTYPE = np.dtype([("id", np.int32), ("rotation", np.int32), ("hamming", np.int32), ("refined", np.int32), ("label", np.int32), ("area", np.int32),
+                         ("corners", np.float64, (4, 2)), ("x", np.float64), ("y", np.float64)], align=True)
+MARKER_COMPONENT_DTYPE = np.dtype([("label", np.int32), ("area", np.int32), ("x0", np.int32), ("y0", np.int32), ("x1", np.int32), ("y1", np.int32),
+                                   ("ext", np.int32, (8, 2))], align=True)
+
+
+class MarkerList(C.Structure):          # lifcal_marker_list
+    _fields_ = [("capacity", C.c_uint64), ("n", C.c_uint64), ("markers", C.c_void_p), ("n_candidates", C.c_uint64), ("seconds", C.c_double)]
+
+
+class MarkerComponents(C.Structure):    # lifcal_marker_components
+    _fields_ = [("dark", C.c_void_p), ("labels", C.c_void_p), ("capacity", C.c_uint64), ("n", C.c_uint64), ("comp", C.c_void_p), ("seconds", C.c_double)]
+
+
+class Constraints(C.Structure):         # lifcal_constraints
+    _fields_ = [("capacity", C.c_uint64), ("n", C.c_uint64), ("id1", uptr), ("id2", uptr), ("distance", dptr), ("sigma", dptr),
+                ("ids_capacity", C.c_uint64), ("n_ids", C.c_uint64), ("ids", uptr)]
+
+
+class MarkerSeeds(C.Structure):         # lifcal_marker_seeds
+    _fields_ = [("capacity", C.c_uint64), ("n_ids", C.c_uint64), ("n_unseeded", C.c_uint64), ("ids", uptr), ("xyz", dptr), ("seeded", C.POINTER(C.c_uint8))]
+
+
+# every symbol include/lifcal_markers.h declares
+MARKERS_PROTOTYPES = {
+    "lifcal_markers_check": (C.c_int, [C.POINTER(RawDepthImage), C.POINTER(MarkerDictionary), C.POINTER(MarkersOptions), C.POINTER(MarkersPlan)]),
+    "lifcal_markers_detect": (C.c_int, [C.POINTER(RawDepthImage), C.c_void_p, C.c_int32, C.POINTER(MarkerDictionary), C.POINTER(MarkersOptions),
+                                        C.POINTER(MarkerList)]),
+    "lifcal_markers_components": (C.c_int, [C.POINTER(RawDepthImage), C.c_void_p, C.c_int32, C.POINTER(MarkersOptions), C.POINTER(MarkerComponents)]),
+    "lifcal_marker_dictionary_distance": (C.c_int, [C.POINTER(MarkerDictionary), _iptr]),
+    "lifcal_marker_dictionary_generate": (C.c_int, [C.c_int32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint64), _iptr]),
+    "lifcal_constraints_read": (C.c_int, [C.c_char_p, C.POINTER(Constraints)]),
+    "lifcal_markers_seed_points": (C.c_int, [C.c_uint64, dptr, dptr, uptr, uptr, C.c_uint64, dptr, dptr, uptr, uptr, C.c_uint64, dptr,
+                                             C.POINTER(MarkerSeeds)]),
+    "lifcal_scene_scale_factor": (C.c_int, [dptr, dptr, C.c_double, dptr]),
+}
+
 # every symbol include/lifcal_prior.h declares
 PRIOR_PROTOTYPES = {
     "lifcal_ba_check_point_priors": (C.c_int, [C.c_uint32, C.POINTER(PointPriors)]),
@@ -757,7 +809,7 @@ def load_library(path: str = LIB_PATH) -> C.CDLL:
                 "`python -c 'import __graft_entry__ as g; g.build()'` (hipcc --offload-arch=gfx950). "
                 "There is no CPU fallback for the bundle-adjustment path.")
         lib = C.CDLL(path)
-        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()) + list(TOTALFOCUS_PROTOTYPES.items()) + list(FEATURES_PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()):
+        for name, (res, args) in list(PROTOTYPES.items()) + list(MLA_PROTOTYPES.items()) + list(IO_PROTOTYPES.items()) + list(COLMAP_PROTOTYPES.items()) + list(DEPTH_PROTOTYPES.items()) + list(HOST_PROTOTYPES.items()) + list(RESECT_PROTOTYPES.items()) + list(INTERSECT_PROTOTYPES.items()) + list(START_PROTOTYPES.items()) + list(REGISTER_PROTOTYPES.items()) + list(PRIOR_PROTOTYPES.items()) + list(ALIGN_PROTOTYPES.items()) + list(GRID_PROTOTYPES.items()) + list(RAWDEPTH_PROTOTYPES.items()) + list(DEPTHMAP_PROTOTYPES.items()) + list(TOTALFOCUS_PROTOTYPES.items()) + list(FEATURES_PROTOTYPES.items()) + list(VERIFY_PROTOTYPES.items()) + list(MARKERS_PROTOTYPES.items()):
             fn = getattr(lib, name)   # AttributeError if a declared symbol is not exported
             fn.restype = res
             fn.argtypes = args
